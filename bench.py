@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """bench.py -- k-mers counted per second at k=12 on synthetic 150-bp reads (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A step = one pass of the hot path (record geometry + 2-bit encode + 4^k histogram) over one batch of
 10 M synthetic 150-bp reads (BASELINE config 2) that is already resident in HBM.  Each rank (one per
 GPU) counts its own batch into its own 4^k uint64 vector (weak scaling, no data-path collective);
 for N > 1 the job ends with ONE chunked RCCL reduce of the vector to rank 0 over xGMI, inside the timed
 region.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps (with the roofline of those steps) and prints the line.
+--full adds everything else: the memory-pattern ceilings, the other timed regions (other modes, ragged
+reads, H2D-fed, FASTQ end to end, .kdb rows), the CPU baseline with its oracle checks, the vector's
+sha256 and the other BASELINE configurations; --no-cpu-baseline / --no-extra-regions / --no-configs
+leave parts of it out.  --dump-outputs DIR writes what one step computes (see dump_outputs).
 
 `python bench.py --gpus N` without a launcher starts its own N rank processes (fresh children, created
 before anything in this process touches torch or HIP); under torch.distributed.run it uses the ranks it
@@ -43,11 +49,18 @@ def parse_args():
     ap.add_argument("--distinct-batches", type=int, default=0,
                     help="resident batches (different seeds) the steps rotate through; 0 = 1 for k <= 12 (BASELINE config 2 is ONE 10 M-read batch), "
                          "8 for k = 13..16, 16 for k = 17: the deferred histogram pass of a flush must see distinct reads")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other single-GPU BASELINE configs (3, 5, config 4's shard, k = 17 steady state)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-regions", action="store_true", help="skip the H2D-fed / FASTQ end-to-end / other-mode regions")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: pattern ceilings, extra timed regions, CPU baseline, vector sha256, other BASELINE configs")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the other single-GPU BASELINE configs (3, 5, config 4's shard, k = 17 steady state)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra-regions", action="store_true", help="with --full: skip the pattern ceilings and the H2D-fed / FASTQ end-to-end / other-mode regions")
     ap.add_argument("--cpu-sample-reads", type=int, default=0, help="0 = size the sample for ~12 s of CPU work")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what one step computes as DIR/<name>.npy (float64; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args):
@@ -605,6 +618,38 @@ def opt_or_none(eng, name):
         return None
 
 
+DUMP_SAMPLE_BINS = 1 << 21        # bins of the count vector --dump-outputs writes (all of them for k <= 10)
+DUMP_BLOCKS = 1 << 20             # block sums that cover every bin of the vector
+DUMP_SEED = 20251016
+
+
+def dump_outputs(torch, np, eng, table, batch, nbytes, n_reads, k, out_dir):
+    """--dump-outputs: what the timed path computes in one step, the same for the same arguments, so that two builds can be compared
+    output for output.  The engine's vector holds the sum of every warm-up and timed step (k >= 13: the number of untimed cycles that let
+    the arena reach its size depends on the free HBM) and, for N > 1, the other ranks' vectors; so it is cleared and the batch of the last
+    timed step is counted once more through the same engine, untimed.  Written as float64 (counts are exact below 2^53), 40 MiB at most:
+      counts_sample_ids    k-mer ids of a fixed, seeded sample of DUMP_SAMPLE_BINS bins, ascending (every bin when 4^k is no larger)
+      counts_sample        their counts
+      counts_block_sums    the vector summed over min(4^k, DUMP_BLOCKS) equal consecutive blocks: every bin is in one
+      totals               [total k-mers, unique k-mers] as kdb_finish returns them"""
+    b, o = batch
+    eng.reset()
+    eng.submit_device(b.data_ptr(), nbytes, o.data_ptr(), n_reads)
+    _, total, unique = eng.finish(copy=False)          # (syncs the engine; checks Sum(counts) == k-mers emitted)
+    nbins = 4 ** k
+    if nbins <= DUMP_SAMPLE_BINS:
+        ids = np.arange(nbins, dtype=np.int64)
+    else:
+        ids = np.sort(np.random.default_rng(DUMP_SEED).choice(nbins, DUMP_SAMPLE_BINS, replace=False)).astype(np.int64)
+    sample = table[torch.from_numpy(ids).to(table.device)].cpu().numpy()
+    blocks = table.view(min(nbins, DUMP_BLOCKS), -1).sum(dim=1).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"counts_sample_ids": ids, "counts_sample": sample, "counts_block_sums": blocks, "totals": np.array([total, unique])}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.astype(np.float64))
+    return sorted(arrays)
+
+
 def committed_counters(k, n_reads, L, canonical, algo):
     """HBM bytes and LDS counters of one step from the committed rocprofv3 PMC passes (profiles/), only when they were
     taken on this exact workload."""
@@ -820,6 +865,13 @@ def main():
             dist.destroy_process_group()
         return
 
+    vector_sha256 = None
+    if args.full and k <= 13:     # sha256 of the little-endian uint64 vector of the whole job (after the reduce for N > 1)
+        import hashlib
+        vector_sha256 = hashlib.sha256(table.cpu().numpy().tobytes()).hexdigest()
+    if args.dump_outputs:         # (clears the vector: after everything that reads the whole job's counts)
+        dump_outputs(torch, np, eng, table, batches[(step_no[0] - 1) % D], nbytes, n_reads, k, args.dump_outputs)
+
     # ---- roofline (HIP events on the engine's compute stream + the engine's own byte counters, both of THIS run) ----
     tc = {n: (traffic1[n] - traffic0[n]) / args.steps for n in traffic1}        # per step, over the timed region
     per_kernel, step_ms, kern, kbytes = per_kernel_table(prof, tc, k, args.steps, n_reads)
@@ -873,7 +925,7 @@ def main():
                                "frac_of_peak": round(alg_bytes_step / (per_step_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
                                "note": "a virtual bandwidth (> 1 is possible); not a roofline"}}
     # ---- what the memory system of THIS box delivers for the kernels' access patterns with no compute (kdb_hbm_pattern_probe) ----
-    if world == 1 and not args.no_extra_regions:
+    if world == 1 and args.full and not args.no_extra_regions:
         try:
             roofline["pattern_ceilings"] = pattern_ceilings(kmerdb_amd, local, k, per_kernel)
         except (MemoryError, RuntimeError, ValueError) as e:      # (8 GiB of scratch beside a 128 GiB vector: a diagnostic must not end the run)
@@ -889,14 +941,14 @@ def main():
                          "source": lds.get("source") or ("profiles/lds_k%d.json (tools/profile_gpu.sh; summary: profiles/r04/rocprof_k%d_summary.md)" % (k, k)), "note": "from a committed rocprofv3 PMC pass of this workload (profiles/), not measured in this run"}
 
     regions, ragged = None, None
-    if world == 1 and not args.no_extra_regions and k <= 13:
+    if world == 1 and args.full and not args.no_extra_regions and k <= 13:
         regions = {"resident": {"ms": round(elapsed / args.steps * 1e3, 4), "gbase_per_s": round(args.steps * nbytes / elapsed / 1e9, 3)}}
         regions.update(extra_regions(kmerdb_amd, np, torch, d_bases, d_offs, n_reads, L, k, canonical, local, args.algo, opts))
         ragged = regions.pop("_ragged", None)
 
     # ---- CPU baseline: the oracle (a port of the reference's per-window loop) on a bounded sample ---
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and k <= 15:      # (the oracle's dense host vector is 4^k * 8 bytes)
+    if world == 1 and args.full and not args.no_cpu_baseline and k <= 15:      # (the oracle's dense host vector is 4^k * 8 bytes)
         from oracle import kmer_oracle
         kmer_oracle.build()
         try:
@@ -1002,11 +1054,10 @@ def main():
         "timed_regions": regions,
         "cpu_baseline": cpu,
     }
-    if k <= 13:     # sha256 of the little-endian uint64 vector of the whole job (after the reduce for N > 1)
-        import hashlib
-        out["vector_sha256"] = hashlib.sha256(table.cpu().numpy().tobytes()).hexdigest()
-    if world == 1 and not args.no_configs and k == 12 and args.algo == 0 and not args.opt and canonical and not args.expand and n_reads == 10_000_000 and L == 150:
-        # the default run also carries BASELINE.json's other single-GPU configurations (the headline's buffers are released first)
+    if vector_sha256 is not None:
+        out["vector_sha256"] = vector_sha256
+    if world == 1 and args.full and not args.no_configs and k == 12 and args.algo == 0 and not args.opt and canonical and not args.expand and n_reads == 10_000_000 and L == 150:
+        # the --full run also carries BASELINE.json's other single-GPU configurations (the headline's buffers are released first)
         del table, batches, d_bases, d_offs
         torch.cuda.empty_cache()
         t_cfg = time.perf_counter()

@@ -93,7 +93,7 @@ def test_bench_launches_its_own_two_ranks_k12(gpu_engine_cls, shape):
     per-rank engines, the untimed probe of the reduce shapes, one reduce of the vector inside the timed region, rank 0
     checks Sum(counts) of the reduced vector against every window of every rank's steps (bench.py asserts it)."""
     d = _bench(["--gpus", "2", "--backend", "gloo", "--k", "12", "--reads", "300000", "--steps", "3", "--warmup", "1",
-                "--no-cpu-baseline", "--no-extra-regions", "--reduce-shape", shape], 600)
+                "--full", "--no-cpu-baseline", "--no-extra-regions", "--reduce-shape", shape], 600)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["steps"] == 3
     assert [r["world_size_seen"] for r in d["per_rank"]] == [2, 2]
     assert d["reduce_calls"] == 1 and d["reduce_ms"] > 0 and d["reduce_shape"] in ("ring", "rs_gather", "a2a_gather")
