@@ -19,6 +19,7 @@
 #include "kdb_kernels.hip.h"
 #include "kdb_hist.hip.h"
 #include "kdb_scatter.hip.h"
+#include "kdb_scatter_host.hip.h"
 #include "kdb_smallk.hip.h"
 #include "kdb_probe.hip.h"
 #include "kdb_hostparse.cpp.h"
@@ -139,7 +140,7 @@ struct kdb_engine {
     int64_t algo = 0;                 // 0 auto, 1 direct atomics, 2 LDS-histogram paths
     int min_len = 0;                  // records shorter than this are an error (0 = k)
     int smallk_old = 0;               // 1: k <= 7 through count_lds_kernel and k = 8 through the paged scatter, as before round 4 (for comparison)
-    int one_level_max_k = kdb::SC1_K; // largest k counted with one scatter level (13: the 1024-ring kernel; 12: k = 13 takes the two-level path, for comparison)
+    kdb::PagedOptions opt;            // tuning options of the paged-scatter paths: written by kdb_set_option alone, read by the host code of those paths
     kdb::ScatterState sc;             // scratch of the paged-scatter path (8 <= k <= 12)
     // the one-level path with the scatter kernel of batch i + 1 beside the histogram pass of batch i ("overlap" option; DROP mode)
     int overlap = 0;                  // 0 off, 1 on
@@ -399,34 +400,32 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
     int algo = (int)e->algo;
     if (algo == 0 || algo == 3) algo = 2;                    // LDS-histogram paths unless told otherwise (3: the paged scatter's old number)
     if (no_first_rec && algo == 2) { algo = 1; e->oom_fallbacks++; e->tp.table_is_zero = false; }
-    const bool paged2 = algo == 2 && e->k > e->one_level_max_k;
+    const bool paged2 = algo == 2 && e->k > e->opt.one_level_max_k;
     // only the deferred two-level flush may treat the vector as still all zero; everything else adds to it right away
-    if (!paged2 || e->n_mode == KDB_N_EXPAND || !e->tp.defer) e->tp.table_is_zero = false;
+    if (!paged2 || e->n_mode == KDB_N_EXPAND || !e->opt.defer) e->tp.table_is_zero = false;
     if (algo == 2) {
         EngineProf hook(e);
         const bool ex = e->n_mode == KDB_N_EXPAND;
+        const kdb::ScBatch batch{d_bases, nbytes, rs, e->k, e->canonical, ex, e->d_table, e->d_ctr};
         int rc;
         if (e->k <= kdb::SMALLK_LDS_MAX_K && !e->smallk_old)
-            rc = kdb::smallk_lds_count(e->s_compute, d_bases, nbytes, rs, e->k, e->canonical, ex, e->sc.grid, e->d_table, e->d_ctr, hook);
+            rc = kdb::smallk_lds_count(e->s_compute, d_bases, nbytes, rs, e->k, e->canonical, ex, e->opt.grid, e->d_table, e->d_ctr, hook);
         else if (e->k <= kdb::SMALLK_MAX) {
             mark();
             rc = kdb::smallk_count(e->s_compute, d_bases, nbytes, e->k, e->canonical, ex, e->d_table, e->d_ctr, hook);
             unmark();
         }
-        else if (e->k <= e->one_level_max_k) {
+        else if (e->k <= e->opt.one_level_max_k) {
             rc = 3;
-            if (e->overlap && e->s_hist && !ex) {
-                e->ov.sc[0].grid = e->sc.grid; e->ov.sc[0].lo_bits = e->sc.lo_bits; e->ov.sc[0].contig_pages = e->sc.contig_pages; e->ov.sc[0].wide_lines = e->sc.wide_lines;
-                rc = kdb::scatter_count_overlapped(e->ov, e->s_compute, e->s_hist, d_bases, nbytes, rs, e->k, e->canonical, e->d_table, e->d_ctr, hook);
-            }
+            if (e->overlap && e->s_hist && !ex) rc = kdb::scatter_count_overlapped(e->ov, e->opt, e->s_compute, e->s_hist, batch, hook);
             if (rc == 3) {
                 { const int jrc = overlap_join(e); if (jrc != KDB_OK) return jrc; }
-                rc = kdb::scatter_count(e->sc, e->s_compute, d_bases, nbytes, rs, e->k, e->canonical, ex, e->d_table, e->d_ctr, hook);
+                rc = kdb::scatter_count(e->sc, e->opt, e->s_compute, batch, hook);
             }
         }
         else {
             const size_t lost = nreads * (size_t)(e->k - 1);
-            rc = kdb::twolevel_paged_count(e->tp, e->s_compute, d_bases, nbytes, rs, nbytes > lost ? nbytes - lost : 0, e->k, e->canonical, ex, e->d_table, e->d_ctr, hook);
+            rc = kdb::twolevel_paged_count(e->tp, e->opt, e->s_compute, batch, nbytes > lost ? nbytes - lost : 0, hook);
         }
         if (rc == 2) { e->oom_fallbacks++; algo = 1; e->tp.table_is_zero = false; }   // no room for the scatter scratch: count this batch with direct atomics
         else if (rc != 0) return fail(KDB_ERR_HIP, "LDS-histogram path failed: %s", kdb::partition_error());
@@ -466,7 +465,7 @@ int flush_pending_paged(kdb_engine *e)
 {
     if (e->tp.pending == 0) return KDB_OK;
     EngineProf hook(e);
-    if (kdb::twolevel_paged_flush(e->tp, e->s_compute, e->d_table, e->d_ctr, hook)) return fail(KDB_ERR_HIP, "LDS-histogram path failed: %s", kdb::partition_error());
+    if (kdb::twolevel_paged_flush(e->tp, e->opt, e->s_compute, e->d_table, e->d_ctr, hook)) return fail(KDB_ERR_HIP, "LDS-histogram path failed: %s", kdb::partition_error());
     return KDB_OK;
 }
 
@@ -574,6 +573,76 @@ const ProbePattern PROBES[] = {
 };
 #undef KDB_PROBE
 constexpr int N_PROBES = (int)(sizeof(PROBES) / sizeof(PROBES[0]));
+}  // namespace
+
+// ---- the engine's plain integer options (kdb_set_option / kdb_get_option): one row each; the odd ones are code in those two functions ----
+namespace {
+enum OptBefore { OPT_NOTHING, OPT_FLUSH_PENDING /* pending batches were scattered under the old value */, OPT_SYNC_AND_STREAMS /* kdb_sync, then overlap_streams */,
+                 OPT_NO_STAGING /* refused once the staging buffers exist */ };
+struct OptRow {
+    const char *name;
+    int64_t (*get)(kdb_engine *);
+    void (*set)(kdb_engine *, int64_t) = nullptr;               // null: read-only
+    bool boolean = false;                                       // stored as 0 / 1
+    int64_t lo = INT64_MIN, hi = INT64_MAX;                     // what kdb_set_option accepts
+    OptBefore before = OPT_NOTHING;                             // what must happen before the value changes
+    const char *hint = "";                                      // the end of the message that refuses a value
+    int64_t multiple_of = 1;
+};
+#define KDB_OPT_RO(field) [](kdb_engine *e) { return (int64_t)e->field; }
+#define KDB_OPT(field) KDB_OPT_RO(field), [](kdb_engine *e, int64_t v) { e->field = (decltype(e->field))v; }
+const OptRow OPTIONS[] = {
+    {"algo", KDB_OPT(algo), false, 0, 3, OPT_NOTHING, " (0 auto, 1 direct atomics, 2 LDS-histogram paths)"},
+    {"min_len", KDB_OPT(min_len), false, 0, 64},
+    {"copy_threads", KDB_OPT(copy_threads), false, 1, 64},
+    {"smallk_old", KDB_OPT(smallk_old), true},
+    {"accum_bytes", KDB_OPT(accum_bytes), false, -1, INT64_MAX, OPT_NO_STAGING, " (-1 auto, 0 off, else bytes)"},
+    {"stage_bytes", KDB_OPT(stage_bytes), false, 4096, INT64_MAX, OPT_NO_STAGING, " (>=4096, multiple of 16)", 16},
+    {"stage_reads", KDB_OPT(stage_reads), false, 1, INT64_MAX, OPT_NO_STAGING},
+    {"overlap", KDB_OPT(overlap), true, 0, 1024, OPT_SYNC_AND_STREAMS},
+    {"overlap_hist_cus", KDB_OPT(overlap_hist_cus), false, 0, 1024, OPT_SYNC_AND_STREAMS},
+    {"overlap_mask_mode", KDB_OPT(overlap_mask_mode), false, 0, 1024, OPT_SYNC_AND_STREAMS},
+    // the paged paths' tuning (kdb::PagedOptions)
+    {"sc_grid", KDB_OPT(opt.grid), false, 0, 1024, OPT_NOTHING, " (0..1024)"},
+    // id = [ hi ][ bucket fields ][ lo ]: how many of a bucket's 15 (k = 17: 16) bin bits sit below the bucket field
+    {"sc_lo_bits", KDB_OPT(opt.lo_bits), false, 0, kdb::SC_LO_BITS_MAX, OPT_FLUSH_PENDING, " (0 = the default of the path, 1..15)"},
+    {"sc_contig_pages", KDB_OPT(opt.contig_pages), true},
+    {"sc_wide_lines", KDB_OPT(opt.wide_lines), true},
+    {"l1_wide_lines", KDB_OPT(opt.l1_wide), true},
+    {"l2_wide_lines", KDB_OPT(opt.l2_wide), true},
+    {"l1_one_round", KDB_OPT(opt.l1_one_round), true},
+    {"l1_compiled_k", KDB_OPT(opt.l1k), true},
+    {"one_level_max_k", KDB_OPT(opt.one_level_max_k), false, 12, kdb::SC1_K, OPT_FLUSH_PENDING, " (12 or 13)"},
+    {"defer_flush", KDB_OPT(opt.defer), true},
+    {"pending_budget", KDB_OPT(opt.budget_bytes), false, 0, INT64_MAX},
+    {"reserve_bytes", KDB_OPT(opt.reserve_bytes), false, 0, INT64_MAX},
+    {"arena_grow", KDB_OPT(opt.grow), false, 0, 2, OPT_NOTHING, " (0 never, 1 when it pays, 2 whenever the arena has filled up)"},
+    {"arena_batches", KDB_OPT(opt.first_batches), false, 1, kdb::PAGED_PENDING_MAX, OPT_NOTHING, " (1..64: the arena's first size, in batches like the first one)"},
+    // what the engine reports
+    {"k", KDB_OPT_RO(k)},
+    {"arena_budget_bytes", [](kdb_engine *e) { return (int64_t)(e->opt.budget_bytes ? e->opt.budget_bytes : e->tp.budget_decided); }},
+    {"free_at_sizing", KDB_OPT_RO(tp.free_at_sizing)},
+    {"overlap_scatter_grid", KDB_OPT_RO(ov.grid)},
+    {"oom_fallbacks", KDB_OPT_RO(oom_fallbacks)},
+    {"pending_batches", KDB_OPT_RO(tp.pending)},
+    {"d2h_bytes", KDB_OPT_RO(d2h_bytes)},
+    {"folded_files", KDB_OPT_RO(folded_files)},
+    {"bytes_in", KDB_OPT_RO(bytes_in)},
+    {"arena_pages", KDB_OPT_RO(tp.arena.cap)},
+    {"arena_reallocs", KDB_OPT_RO(tp.reallocs)},
+    {"hist_flushes", KDB_OPT_RO(tp.flushes)},
+    {"flushed_batches", KDB_OPT_RO(tp.flushed_batches)},
+    {"full_flushes", KDB_OPT_RO(tp.full_flushes)},
+};
+#undef KDB_OPT
+#undef KDB_OPT_RO
+static_assert(kdb::SC_LO_BITS_MAX == 15 && kdb::SC1_K == 13 && kdb::PAGED_PENDING_MAX == 64, "the hints of sc_lo_bits, one_level_max_k and arena_batches spell these out");
+
+const OptRow *find_option(const char *name)
+{
+    for (const OptRow &row : OPTIONS) if (!strcmp(name, row.name)) return &row;
+    return nullptr;
+}
 }  // namespace
 
 extern "C" {
@@ -1514,127 +1583,39 @@ int kdb_hbm_pattern_probe(int device_id, double *gb_per_s_out, int n_out)
 int kdb_set_option(kdb_engine *e, const char *name, int64_t value)
 {
     if (!e || !name) return fail(KDB_ERR_ARG, "NULL argument");
-    if (!strcmp(name, "algo")) {
-        if (value < 0 || value > 3) return fail(KDB_ERR_ARG, "algo=%lld (0 auto, 1 direct atomics, 2 LDS-histogram paths)", (long long)value);
-        e->algo = value; return KDB_OK;
-    }
-    if (!strcmp(name, "defer_flush")) {
-        DeviceGuard g(e->device);
-        if (!value) { int rc = flush_pending_paged(e); if (rc != KDB_OK) return rc; }
-        e->tp.defer = value ? 1 : 0; return KDB_OK;
-    }
-    if (!strcmp(name, "pending_budget")) {
-        if (value < 0) return fail(KDB_ERR_ARG, "pending_budget=%lld", (long long)value);
-        e->tp.budget_bytes = (size_t)value; return KDB_OK;
-    }
-    if (!strcmp(name, "l1_compiled_k")) { e->tp.l1k = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "l1_wide_lines")) { e->tp.l1_wide = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "l1_one_round")) { e->tp.l1_one_round = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "l2_wide_lines")) { e->tp.l2_wide = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "reserve_bytes")) {
-        if (value < 0) return fail(KDB_ERR_ARG, "reserve_bytes=%lld", (long long)value);
-        e->tp.reserve_bytes = (size_t)value; return KDB_OK;
-    }
-    if (!strcmp(name, "arena_grow")) {
-        if (value < 0 || value > 2) return fail(KDB_ERR_ARG, "arena_grow=%lld (0 never, 1 when it pays, 2 whenever the arena has filled up)", (long long)value);
-        e->tp.grow = (int)value; return KDB_OK;
-    }
-    if (!strcmp(name, "smallk_old")) { e->smallk_old = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "one_level_max_k")) {
-        if (value != 12 && value != kdb::SC1_K) return fail(KDB_ERR_ARG, "one_level_max_k=%lld (12 or %d)", (long long)value, kdb::SC1_K);
-        DeviceGuard g(e->device);
-        { int rc = flush_pending_paged(e); if (rc != KDB_OK) return rc; }
-        e->one_level_max_k = (int)value; return KDB_OK;
-    }
-    if (!strcmp(name, "arena_batches")) {
-        if (value < 1 || value > kdb::PAGED_PENDING_MAX) return fail(KDB_ERR_ARG, "arena_batches=%lld (1..%d: the arena's first size, in batches like the first one)", (long long)value, kdb::PAGED_PENDING_MAX);
-        e->tp.first_batches = (int)value; return KDB_OK;
-    }
-    if (!strcmp(name, "sc_grid")) {
-        if (value < 0 || value > 1024) return fail(KDB_ERR_ARG, "sc_grid=%lld (0..1024)", (long long)value);
-        e->sc.grid = (int)value; e->tp.l1.grid = (int)value; return KDB_OK;
-    }
-    if (!strcmp(name, "overlap") || !strcmp(name, "overlap_hist_cus") || !strcmp(name, "overlap_mask_mode")) {
-        if (value < 0 || value > 1024) return fail(KDB_ERR_ARG, "%s=%lld", name, (long long)value);
-        DeviceGuard g(e->device);
-        { int rc = kdb_sync(e); if (rc != KDB_OK) return rc; }
-        if (!strcmp(name, "overlap")) e->overlap = value ? 1 : 0;
-        else if (!strcmp(name, "overlap_hist_cus")) e->overlap_hist_cus = (int)value;
-        else e->overlap_mask_mode = (int)value;
-        return overlap_streams(e);
-    }
+    // (sc_top_bits=1 is the old name of sc_lo_bits=15: buckets from the leading id bits)
+    if (!strcmp(name, "sc_top_bits")) return kdb_set_option(e, "sc_lo_bits", value ? kdb::SC_LO_BITS_MAX : 0);
 #ifdef KDB_SC_PROF
     if (!strcmp(name, "sc_ablate")) { int v = (int)value; (void)hipMemcpyToSymbol(HIP_SYMBOL(kdb::g_sc_ablate), &v, sizeof v); return KDB_OK; }
 #endif
-    if (!strcmp(name, "sc_lo_bits") || !strcmp(name, "sc_top_bits")) {
-        // id = [ hi ][ bucket fields ][ lo ]: how many of a bucket's 15 (k = 17: 16) bin bits sit below the bucket field
-        // (sc_top_bits=1 is the old name of sc_lo_bits=15: buckets from the leading id bits)
-        int64_t lo = !strcmp(name, "sc_top_bits") ? (value ? kdb::SC_LO_BITS_MAX : 0) : value;
-        if (lo < 0 || lo > kdb::SC_LO_BITS_MAX) return fail(KDB_ERR_ARG, "sc_lo_bits=%lld (0 = the default of the path, 1..%d)", (long long)lo, kdb::SC_LO_BITS_MAX);
+    const OptRow *row = find_option(name);
+    if (!row || !row->set) return fail(KDB_ERR_ARG, "unknown option '%s'", name);
+    if (row->before == OPT_NO_STAGING && e->staging_ready) return fail(KDB_ERR_STATE, "staging already allocated");
+    if (value < row->lo || value > row->hi || value % row->multiple_of) return fail(KDB_ERR_ARG, "%s=%lld%s", name, (long long)value, row->hint);
+    // defer_flush = 0: what is pending is added to the vector now
+    if (row->before == OPT_FLUSH_PENDING || (!strcmp(name, "defer_flush") && !value)) {
         DeviceGuard g(e->device);
-        { int rc = flush_pending_paged(e); if (rc != KDB_OK) return rc; }        // (pending batches were scattered with the old split)
-        e->sc.lo_bits = (int)lo; e->tp.l1.lo_bits = (int)lo; return KDB_OK;
+        int rc = flush_pending_paged(e);
+        if (rc != KDB_OK) return rc;
     }
-    if (!strcmp(name, "sc_contig_pages")) { e->sc.contig_pages = value ? 1 : 0; e->tp.l1.contig_pages = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "sc_wide_lines")) { e->sc.wide_lines = value ? 1 : 0; return KDB_OK; }
-    if (!strcmp(name, "accum_bytes")) {
-        if (e->staging_ready) return fail(KDB_ERR_STATE, "staging already allocated");
-        if (value < -1) return fail(KDB_ERR_ARG, "accum_bytes=%lld (-1 auto, 0 off, else bytes)", (long long)value);
-        e->accum_bytes = value; return KDB_OK;
-    }
-    if (!strcmp(name, "stage_bytes")) {
-        if (e->staging_ready) return fail(KDB_ERR_STATE, "staging already allocated");
-        if (value < 4096 || (value & 15)) return fail(KDB_ERR_ARG, "stage_bytes=%lld (>=4096, multiple of 16)", (long long)value);
-        e->stage_bytes = (size_t)value; return KDB_OK;
-    }
-    if (!strcmp(name, "min_len")) {
-        if (value < 0 || value > 64) return fail(KDB_ERR_ARG, "min_len=%lld", (long long)value);
-        e->min_len = (int)value; return KDB_OK;
-    }
-    if (!strcmp(name, "copy_threads")) {
-        if (value < 1 || value > 64) return fail(KDB_ERR_ARG, "copy_threads=%lld", (long long)value);
-        e->copy_threads = (int)value; return KDB_OK;
-    }
-    if (!strcmp(name, "stage_reads")) {
-        if (e->staging_ready) return fail(KDB_ERR_STATE, "staging already allocated");
-        if (value < 1) return fail(KDB_ERR_ARG, "stage_reads=%lld", (long long)value);
-        e->stage_reads = (size_t)value; return KDB_OK;
-    }
-    return fail(KDB_ERR_ARG, "unknown option '%s'", name);
+    if (!strcmp(name, "pending_budget")) e->tp.budget_decided = 0;      // (pending_budget = 0: the arena's size is decided anew at its next use)
+    if (row->before != OPT_SYNC_AND_STREAMS) { row->set(e, row->boolean ? (value ? 1 : 0) : value); return KDB_OK; }
+    DeviceGuard g(e->device);
+    { int rc = kdb_sync(e); if (rc != KDB_OK) return rc; }
+    row->set(e, row->boolean ? (value ? 1 : 0) : value);
+    return overlap_streams(e);
 }
 
 int kdb_get_option(kdb_engine *e, const char *name, int64_t *value)
 {
     if (!e || !name || !value) return fail(KDB_ERR_ARG, "NULL argument");
-    if (!strcmp(name, "algo")) { *value = e->algo; return KDB_OK; }
-    if (!strcmp(name, "reserve_bytes")) { *value = (int64_t)e->tp.reserve_bytes; return KDB_OK; }
-    if (!strcmp(name, "arena_budget_bytes")) { *value = (int64_t)e->tp.budget_bytes; return KDB_OK; }
-    if (!strcmp(name, "free_at_sizing")) { *value = (int64_t)e->tp.free_at_sizing; return KDB_OK; }
+    if (const OptRow *row = find_option(name)) { *value = row->get(e); return KDB_OK; }
     if (!strcmp(name, "free_hbm")) {
         DeviceGuard g(e->device);
         size_t free_b = 0, total_b = 0;
         HIP_TRY(hipMemGetInfo(&free_b, &total_b));
         *value = (int64_t)free_b; return KDB_OK;
     }
-    if (!strcmp(name, "overlap")) { *value = e->overlap; return KDB_OK; }
-    if (!strcmp(name, "overlap_hist_cus")) { *value = e->overlap_hist_cus; return KDB_OK; }
-    if (!strcmp(name, "overlap_scatter_grid")) { *value = e->ov.grid; return KDB_OK; }
-    if (!strcmp(name, "stage_bytes")) { *value = (int64_t)e->stage_bytes; return KDB_OK; }
-    if (!strcmp(name, "stage_reads")) { *value = (int64_t)e->stage_reads; return KDB_OK; }
-    if (!strcmp(name, "k")) { *value = e->k; return KDB_OK; }
-    if (!strcmp(name, "defer_flush")) { *value = e->tp.defer; return KDB_OK; }
-    if (!strcmp(name, "sc_lo_bits")) { *value = e->sc.lo_bits; return KDB_OK; }
-    if (!strcmp(name, "sc_contig_pages")) { *value = e->sc.contig_pages; return KDB_OK; }
-    if (!strcmp(name, "sc_wide_lines")) { *value = e->sc.wide_lines; return KDB_OK; }
-    if (!strcmp(name, "l1_wide_lines")) { *value = e->tp.l1_wide; return KDB_OK; }
-    if (!strcmp(name, "l2_wide_lines")) { *value = e->tp.l2_wide; return KDB_OK; }
-    if (!strcmp(name, "l1_one_round")) { *value = e->tp.l1_one_round; return KDB_OK; }
-    if (!strcmp(name, "oom_fallbacks")) { *value = e->oom_fallbacks; return KDB_OK; }
-    if (!strcmp(name, "pending_batches")) { *value = (int64_t)e->tp.pending; return KDB_OK; }
-    if (!strcmp(name, "d2h_bytes")) { *value = (int64_t)e->d2h_bytes; return KDB_OK; }
-    if (!strcmp(name, "folded_files")) { *value = (int64_t)e->folded_files; return KDB_OK; }
-    if (!strcmp(name, "bytes_in")) { *value = (int64_t)e->bytes_in; return KDB_OK; }
-    if (!strcmp(name, "arena_pages")) { *value = (int64_t)e->tp.cap2; return KDB_OK; }
     if (!strcmp(name, "arena_used_bound") || !strcmp(name, "arena_worst_case") || !strcmp(name, "arena_cursor")) {
         // pages of the arena the pending batches hold: the host's present bound (worst cases minus what the read-backs of the device's
         // cursor have shown to be unused), the worst cases added up, and the device's cursor itself (synchronises the compute stream)
@@ -1648,14 +1629,6 @@ int kdb_get_option(kdb_engine *e, const char *name, int64_t *value)
         kdb::twolevel_paged_poll(e->tp);
         *value = (int64_t)(!strcmp(name, "arena_worst_case") ? e->tp.used2 : e->tp.used2 - e->tp.slack); return KDB_OK;
     }
-    if (!strcmp(name, "arena_reallocs")) { *value = (int64_t)e->tp.reallocs; return KDB_OK; }
-    if (!strcmp(name, "arena_grow")) { *value = e->tp.grow; return KDB_OK; }
-    if (!strcmp(name, "arena_batches")) { *value = e->tp.first_batches; return KDB_OK; }
-    if (!strcmp(name, "one_level_max_k")) { *value = e->one_level_max_k; return KDB_OK; }
-    if (!strcmp(name, "smallk_old")) { *value = e->smallk_old; return KDB_OK; }
-    if (!strcmp(name, "hist_flushes")) { *value = (int64_t)e->tp.flushes; return KDB_OK; }
-    if (!strcmp(name, "flushed_batches")) { *value = (int64_t)e->tp.flushed_batches; return KDB_OK; }
-    if (!strcmp(name, "full_flushes")) { *value = (int64_t)e->tp.full_flushes; return KDB_OK; }
     {
         // HBM traffic by the engine's own account (cumulative since kdb_reset; the device is synchronised to read them)
         static const struct { const char *name; size_t off; } dev[] = {

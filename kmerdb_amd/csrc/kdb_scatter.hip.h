@@ -1705,695 +1705,4 @@ page_hist_kernel(const uint8_t *__restrict__ pages, const PageEntry *__restrict_
     }
 }
 
-// ---------------------------------------------------------------------------------
-// host: 8 <= k <= 12
-// ---------------------------------------------------------------------------------
-struct ScatterState {
-    uint8_t *d_pages = nullptr; size_t pages_cap = 0, page_bytes = 0;   // in pages of page_bytes
-    uint32_t *d_tag = nullptr;                                  // [pages_cap]
-    PageEntry *d_list = nullptr;                                // [pages_cap]
-    uint32_t *d_bkt = nullptr;                                  // bkt_pages [NB] | bkt_elems [NB] | page_base [NB + 1] | slice_base [NB + 1]
-    size_t bkt_cap = 0;                                         // NB the arrays were sized for
-    int grid = 0;                                               // persistent workgroups (0 = SC_GRID)
-    int lo_bits = 0;                                            // id bits below the bucket field; 0 = SC_LO_BITS_ONE_LEVEL / _TWO_LEVEL (SC_LO_BITS_MAX: buckets from the leading id bits, uneven in canonical mode)
-    int contig_pages = 1;                                       // 1: workgroup w's pages are w * wg_pages + p (level 1 at k = 15: 2.26 -> 2.18 ms), 0: w + p * G
-    int wide_lines = 1;                                         // 1: k <= 12 writes its pages in 128-byte pieces (engine option sc_wide_lines)
-};
-
-inline void scatter_free(ScatterState &st)
-{
-    if (st.d_pages) (void)hipFree(st.d_pages);
-    if (st.d_tag) (void)hipFree(st.d_tag);
-    if (st.d_list) (void)hipFree(st.d_list);
-    if (st.d_bkt) (void)hipFree(st.d_bkt);
-    st = ScatterState();
-}
-
-// tiles per launch: sub-batches of 2 Gi positions (page numbers stay well inside 32 bits), and fewer than 4096 tiles per
-// workgroup (a thread's packed 16 + 16-bit statistics of <= 16 per tile cannot carry)
-inline uint64_t scatter_max_tiles(uint32_t Gmax, uint32_t tile_pos = SC_TILE_POS)
-{
-    const uint64_t a = (1ull << 31) / tile_pos, b = 4095ull * Gmax;
-    return a < b ? a : b;
-}
-
-// pages a workgroup can need: every element it can emit, one partial page per ring, one spare
-inline uint32_t scatter_wg_pages(uint32_t tiles_per_wg, int rings, uint32_t page_elems, uint32_t tile_pos = SC_TILE_POS, uint32_t extra_elems = 0)
-{
-    return (uint32_t)(((uint64_t)tiles_per_wg * tile_pos + extra_elems + page_elems - 1) / page_elems) + (uint32_t)rings + 1u;
-}
-
-// EXPAND mode: fills of N-windows (4 or 16 per window) go through the rings like every other id; a workgroup's page sequence has
-// room for half as many of them as it has window positions (0.5 % N at k = 12 makes a quarter), at least one full pass of
-// 16 per thread; beyond that a workgroup adds its fills to the vector directly
-inline uint32_t scatter_extra_elems(uint32_t tiles_per_wg, uint32_t tile_pos, int n_expand)
-{
-    if (!n_expand) return 0u;
-    const uint64_t half = (uint64_t)tiles_per_wg * tile_pos / 2, floor_ = 16u * 1024u + 1024u * 64u + 2048u;      // (a round of 1024 threads, what the rings hold, slack)
-    const uint64_t v = half > floor_ ? half : floor_;
-    return (uint32_t)(v < 0x7FFFFFFFull ? v : 0x7FFFFFFFull);
-}
-
-inline int scatter_reserve(ScatterState &st, hipStream_t stream, size_t npages, size_t nb, size_t page_bytes = SC_PAGE_BYTES)
-{
-    if (st.pages_cap < npages || st.page_bytes != page_bytes) {
-        if (st.d_pages) { if (hipStreamSynchronize(stream) != hipSuccess) return 1; (void)hipFree(st.d_pages); (void)hipFree(st.d_tag); (void)hipFree(st.d_list); st.d_pages = nullptr; st.d_tag = nullptr; st.d_list = nullptr; st.pages_cap = 0; }
-        if (hipMalloc((void **)&st.d_pages, npages * page_bytes) != hipSuccess ||
-            hipMalloc((void **)&st.d_tag, npages * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc((void **)&st.d_list, npages * sizeof(PageEntry)) != hipSuccess) {
-            (void)hipGetLastError();
-            if (st.d_pages) (void)hipFree(st.d_pages);
-            if (st.d_tag) (void)hipFree(st.d_tag);
-            if (st.d_list) (void)hipFree(st.d_list);
-            st.d_pages = nullptr; st.d_tag = nullptr; st.d_list = nullptr;
-            return 2;
-        }
-        st.pages_cap = npages;
-        st.page_bytes = page_bytes;
-    }
-    if (st.bkt_cap < nb) {
-        if (st.d_bkt) { if (hipStreamSynchronize(stream) != hipSuccess) return 1; (void)hipFree(st.d_bkt); st.d_bkt = nullptr; st.bkt_cap = 0; }
-        if (hipMalloc((void **)&st.d_bkt, (4 * nb + 2) * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return 2; }
-        st.bkt_cap = nb;
-    }
-    return 0;
-}
-
-// k = 13 in ONE level: 26 id bits = 10 bucket bits + 16 bin bits.  1024 rings of 64 u16 elements (128 KiB of LDS) leave room for
-// one workgroup per CU, so that workgroup has 1024 threads (16 waves per CU, as two workgroups of 512 have) and a tile of 1023
-// chunks; a bucket's 65536 bins share the 32768 histogram words as two 16-bit counters each (page_hist_kernel<true>, as at
-// k = 17).  Level 2 of the two-level path existed at k = 13 only to split one more bit pair: 4.48 -> see DESIGN.md section 5.
-constexpr int SC1_THREADS = 1024, SC1_RINGS = 1024, SC1_GRID = 256, SC1_K = 13;
-constexpr int SC1_TILE_POS = (SC1_THREADS - 1) * 16;
-
-// The one-level path in two stages, so that they can run on different streams: stage 1 = the scatter kernel of a sub-batch into the
-// pages of `st`, stage 2 = the page sort and the histogram pass over those pages.  ScGeom: what the host works out once per batch.
-struct ScGeom {
-    bool big; bool wide /* k <= 12 in 128-byte pieces: one workgroup of 1024 threads per CU, 512 rings of 128 elements (u16w) */;
-    int binb, nb, rings, sub_log2, nb_bits, lo_bits, hi_shift;
-    uint32_t tile_stride, tile_pos, Gmax;
-    uint64_t ntiles_all, max_tiles;
-};
-struct ScLaunch { uint32_t nt, G, npages; };
-
-inline ScGeom scatter_geometry(const ScatterState &st, size_t nbytes, int k, uint32_t grid_default = 0)
-{
-    ScGeom g;
-    g.big = k == SC1_K;                                                  // 1024 threads, 1024 rings, 16-bit bins
-    g.binb = g.big ? 16 : BIN_BITS;
-    g.nb = 1 << (2 * k - g.binb);                                        // buckets: 2 (k = 8) .. 512 (k = 12), 1024 (k = 13)
-    g.rings = g.big ? SC1_RINGS : 512;
-    g.lo_bits = st.lo_bits ? st.lo_bits : SC_LO_BITS_ONE_LEVEL;          // (lo_bits = 15: bucket = leading id bits, for comparison)
-    g.wide = !g.big && st.wide_lines != 0;
-    g.tile_stride = (g.big || g.wide) ? (uint32_t)SC1_THREADS - 1u : (uint32_t)SC_TILE_STRIDE;
-    g.tile_pos = g.tile_stride * 16u;
-    g.sub_log2 = 0; g.nb_bits = 2 * k - g.binb;
-    while ((g.nb << g.sub_log2) < g.rings) g.sub_log2++;                 // few buckets: each gets several rings (no same-address pile-up)
-    g.hi_shift = g.lo_bits + g.nb_bits;
-    g.ntiles_all = ((nbytes + 15) / 16 + g.tile_stride - 1) / g.tile_stride;
-    g.Gmax = st.grid > 0 ? (uint32_t)st.grid : (grid_default ? grid_default : (uint32_t)((g.big || g.wide) ? SC1_GRID : SC_GRID));
-    g.max_tiles = scatter_max_tiles(g.Gmax, g.tile_pos);
-    return g;
-}
-
-// scratch for the largest sub-batch; 0 ok, 1 stream error, 2 no room
-inline int scatter_reserve_for(ScatterState &st, hipStream_t stream, const ScGeom &g, int n_expand)
-{
-    const uint64_t nt = g.ntiles_all < g.max_tiles ? g.ntiles_all : g.max_tiles;
-    const uint32_t G = (uint32_t)(nt < g.Gmax ? nt : g.Gmax);
-    const uint32_t tpw = (uint32_t)((nt + G - 1) / G);
-    const uint32_t wg_pages = scatter_wg_pages(tpw, g.rings, 512, g.tile_pos, scatter_extra_elems(tpw, g.tile_pos, n_expand));
-    const int rc = scatter_reserve(st, stream, (size_t)G * wg_pages, (size_t)g.nb);
-    if (rc == 2) { partition_error_ref() = "scratch allocation failed"; return 2; }
-    if (rc) { partition_error_ref() = "stream error"; return 1; }
-    return 0;
-}
-
-inline int scatter_stage1(ScatterState &st, hipStream_t stream, const ScGeom &g, uint64_t t0, const uint8_t *d_bases, size_t nbytes, const RecStarts &rs, int k,
-                          int canonical, int n_expand, unsigned long long *d_table, DevCounters *d_ctr, ProfHook &prof, ScLaunch *L)
-{
-    constexpr int C = 64;
-    const int nb = g.nb, lo_bits = g.lo_bits, nb_bits = g.nb_bits, sub_log2 = g.sub_log2;
-    const uint32_t nt = (uint32_t)((g.ntiles_all - t0) < g.max_tiles ? (g.ntiles_all - t0) : g.max_tiles);
-    const uint32_t G = nt < g.Gmax ? nt : g.Gmax;
-    ScOut out;
-    out.pages = st.d_pages; out.tag = st.d_tag;
-    out.extra_elems = scatter_extra_elems((nt + G - 1) / G, g.tile_pos, n_expand);
-    out.wg_pages = scatter_wg_pages((nt + G - 1) / G, g.rings, 512, g.tile_pos, out.extra_elems);
-    out.wg_range = nullptr; out.contig = (uint32_t)st.contig_pages; out.wg_base = 0; out.grid = 0;
-    const uint32_t npages = G * out.wg_pages;
-    L->nt = nt; L->G = G; L->npages = npages;
-    if (hipMemsetAsync(st.d_tag, 0xFF, (size_t)npages * sizeof(uint32_t), stream) != hipSuccess ||
-        hipMemsetAsync(st.d_bkt, 0, 2 * (size_t)nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
-    prof.begin_on(KDB_KERNEL_SCATTER, stream);
-#define KDB_LAUNCH_SC1(EL, CC, E, CN, KK, RG, TH, RAG)                                                                                     \
-    hipLaunchKernelGGL((scatter_bases_kernel<uint32_t, EL, RG, CC, 16, E, CN, KK, TH, RAG>), dim3(G), dim3(TH), 0, stream, d_bases,       \
-                       (uint64_t)nbytes, (uint32_t)t0, nt, k, lo_bits, nb_bits, sub_log2, out, d_table, d_ctr, rs)
-#define KDB_LAUNCH_SC(EL, CC, E, CN, KK, RG, TH) do { KDB_LAUNCH_SC1(EL, CC, E, CN, KK, RG, TH, false); KDB_LAUNCH_SC1(EL, CC, E, CN, KK, RG, TH, true); } while (0)
-#define KDB_LAUNCH_SC_MODES(EL, CC, KK, RG, TH)                                                                                            \
-    do {                                                                                                                                   \
-        if (n_expand) { if (canonical) KDB_LAUNCH_SC(EL, CC, true, true, KK, RG, TH); else KDB_LAUNCH_SC(EL, CC, true, false, KK, RG, TH); }   \
-        else          { if (canonical) KDB_LAUNCH_SC(EL, CC, false, true, KK, RG, TH); else KDB_LAUNCH_SC(EL, CC, false, false, KK, RG, TH); } \
-    } while (0)
-    if (g.big) {
-        if (lo_bits == SC_LO_BITS_ONE_LEVEL) KDB_LAUNCH_SC_MODES(uint16_t, C, SC1_K, SC1_RINGS, SC1_THREADS);      // shifts and masks compiled in
-        else                                 KDB_LAUNCH_SC_MODES(uint16_t, C, 0, SC1_RINGS, SC1_THREADS);
-    } else if (g.wide) {
-        // 128-byte pieces: one workgroup of 1024 threads per CU, 512 rings of 128 elements
-        // (shifts, masks and rings per bucket compiled in for the default bucket field: two dozen scalar registers stay free)
-        const bool compiled = lo_bits == SC_LO_BITS_ONE_LEVEL && (nb << sub_log2) == 512;
-        if (compiled && k == 12)      KDB_LAUNCH_SC_MODES(u16w, 128, 12, 512, SC1_THREADS);                                          // BASELINE's headline k
-        else if (compiled && k == 11) KDB_LAUNCH_SC_MODES(u16w, 128, 11, 512, SC1_THREADS);
-        else if (compiled && k == 10) KDB_LAUNCH_SC_MODES(u16w, 128, 10, 512, SC1_THREADS);
-        else if (compiled && k == 9)  KDB_LAUNCH_SC_MODES(u16w, 128, 9, 512, SC1_THREADS);
-        else                          KDB_LAUNCH_SC_MODES(u16w, 128, 0, 512, SC1_THREADS);
-    } else if (k == 12 && lo_bits == SC_LO_BITS_ONE_LEVEL && sub_log2 == 0) {
-        KDB_LAUNCH_SC_MODES(uint16_t, C, 12, 512, SC_THREADS);                                         // ... in 64-byte lines, two workgroups per CU
-    } else {
-        KDB_LAUNCH_SC_MODES(uint16_t, C, 0, 512, SC_THREADS);
-    }
-#undef KDB_LAUNCH_SC_MODES
-#undef KDB_LAUNCH_SC
-#undef KDB_LAUNCH_SC1
-    prof.end();
-    if (hipGetLastError() != hipSuccess) { partition_error_ref() = "paged scatter failed to launch"; return 1; }
-    return 0;
-}
-
-inline int scatter_stage2(ScatterState &st, hipStream_t stream, const ScGeom &g, const ScLaunch &L, unsigned long long *d_table, DevCounters *d_ctr, ProfHook &prof)
-{
-    const int nb = g.nb;
-    const uint32_t npages = L.npages;
-    uint32_t *const bkt_pages = st.d_bkt, *const bkt_elems = st.d_bkt + nb, *const page_base = st.d_bkt + 2 * nb, *const slice_base = st.d_bkt + 3 * nb + 1;
-    prof.begin_on(KDB_KERNEL_PAGE_SORT, stream);
-    const uint32_t pgrid = (npages + 4095u) / 4096u < 256u ? (npages + 4095u) / 4096u : 256u;
-    const uint32_t target = 512u;                                    // P2 workgroups in all (fewer, larger slices win: single-slice buckets flush without atomics)
-    const uint32_t est_pages = (uint32_t)(((uint64_t)L.nt * g.tile_pos * 2) / SC_PAGE_BYTES) + 1u;
-    uint32_t slice_pages = (est_pages + target - 1) / target;
-    if (slice_pages < 128u) slice_pages = 128u;                      // >= 64 Ki elements per histogram
-    hipLaunchKernelGGL(pages_count_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)st.d_tag, npages, (uint32_t)nb, bkt_pages, bkt_elems,
-                       &d_ctr->pages_bases, 32u);
-    hipLaunchKernelGGL(pages_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t *)bkt_pages, (const uint32_t *)bkt_elems, (uint32_t)nb,
-                       page_base, slice_base, slice_pages, d_ctr);
-    hipLaunchKernelGGL(pages_place_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)st.d_tag, npages, (uint32_t)nb, bkt_pages,
-                       (const uint32_t *)page_base, st.d_list);
-    prof.end();
-    prof.begin_on(KDB_KERNEL_PAGE_HIST, stream);
-    const uint32_t p2_grid = npages / slice_pages + (uint32_t)nb + 1u;
-    if (g.big)
-        hipLaunchKernelGGL(page_hist_kernel<true>, dim3(p2_grid), dim3(P2_THREADS), 0, stream, (const uint8_t *)st.d_pages, (const PageEntry *)st.d_list,
-                           (const uint32_t *)page_base, (const uint32_t *)slice_base, (uint32_t)nb, d_table, g.lo_bits, g.hi_shift, 0, d_ctr);
-    else
-        hipLaunchKernelGGL(page_hist_kernel<false>, dim3(p2_grid), dim3(P2_THREADS), 0, stream, (const uint8_t *)st.d_pages, (const PageEntry *)st.d_list,
-                           (const uint32_t *)page_base, (const uint32_t *)slice_base, (uint32_t)nb, d_table, g.lo_bits, g.hi_shift, 0, d_ctr);
-    prof.end();
-    if (hipGetLastError() != hipSuccess) { partition_error_ref() = "paged scatter failed to launch"; return 1; }
-    return 0;
-}
-
-// returns 0 ok, 1 error (partition_error()), 2 no room for the scratch (nothing was counted)
-inline int scatter_count(ScatterState &st, hipStream_t stream, const uint8_t *d_bases, size_t nbytes, const RecStarts &rs, int k, int canonical, int n_expand,
-                         unsigned long long *d_table, DevCounters *d_ctr, ProfHook &prof)
-{
-    const ScGeom g = scatter_geometry(st, nbytes, k);
-    { const int rc = scatter_reserve_for(st, stream, g, n_expand); if (rc) return rc; }
-    for (uint64_t t0 = 0; t0 < g.ntiles_all; t0 += g.max_tiles) {
-        ScLaunch L;
-        if (scatter_stage1(st, stream, g, t0, d_bases, nbytes, rs, k, canonical, n_expand, d_table, d_ctr, prof, &L)) return 1;
-        if (scatter_stage2(st, stream, g, L, d_table, d_ctr, prof)) return 1;
-    }
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------
-// The one-level path with the two stages of CONSECUTIVE batches side by side: the scatter kernel is bound by
-// VALU issue, the histogram pass by HBM and LDS atomics, and on one stream they take turns.  Two sets of pages; batch i's stage 2 runs
-// on a second stream while batch i + 1's stage 1 runs on the first.  The histogram passes stay in order (one stream: their plain
-// read-modify-writes of the vector never meet each other), and a scatter kernel that runs beside a pass leaves its degenerate ids in
-// a side list (hot_add) that is added behind the pass of its own batch.  DROP mode and batches of one sub-batch only (the callers fall
-// back to scatter_count otherwise).  CU masks on the two streams (hipExtStreamCreateWithCUMask) give each stage its own CUs: both stages
-// want most of a CU's LDS, so without masks a pass only finds room where the scatter kernel's persistent workgroups have ended.
-// ---------------------------------------------------------------------------------
-struct OverlapState {
-    ScatterState sc[2];
-    unsigned long long *side[2] = {nullptr, nullptr};
-    size_t side_cap = 0;                                                  // pairs
-    hipEvent_t scattered[2] = {nullptr, nullptr}, hist_done[2] = {nullptr, nullptr};
-    bool used[2] = {false, false};
-    int next = 0, last = -1;                                              // set of the next batch; set whose pass was launched last (-1: none outstanding)
-    uint32_t grid = 0;                                                    // persistent scatter workgroups (0: the usual number)
-};
-
-inline void overlap_free(OverlapState &ov)
-{
-    for (int j = 0; j < 2; j++) {
-        scatter_free(ov.sc[j]);
-        if (ov.side[j]) (void)hipFree(ov.side[j]);
-        if (ov.scattered[j]) (void)hipEventDestroy(ov.scattered[j]);
-        if (ov.hist_done[j]) (void)hipEventDestroy(ov.hist_done[j]);
-    }
-    ov = OverlapState();
-}
-
-// 0 ok, 1 error, 2 no room, 3 this batch does not fit the overlapped form (several sub-batches): count it with scatter_count
-inline int scatter_count_overlapped(OverlapState &ov, hipStream_t s_scatter, hipStream_t s_hist, const uint8_t *d_bases, size_t nbytes, const RecStarts &rs, int k,
-                                    int canonical, unsigned long long *d_table, DevCounters *d_ctr, ProfHook &prof)
-{
-    const int j = ov.next;
-    ScatterState &st = ov.sc[j];
-    st.grid = ov.sc[0].grid; st.lo_bits = ov.sc[0].lo_bits; st.contig_pages = ov.sc[0].contig_pages; st.wide_lines = ov.sc[0].wide_lines;
-    const ScGeom g = scatter_geometry(st, nbytes, k, ov.grid);
-    if (g.ntiles_all > g.max_tiles) return 3;
-    for (int q = 0; q < 2; q++) {
-        if (!ov.scattered[q] && hipEventCreateWithFlags(&ov.scattered[q], hipEventDisableTiming) != hipSuccess) { partition_error_ref() = "event creation failed"; return 1; }
-        if (!ov.hist_done[q] && hipEventCreateWithFlags(&ov.hist_done[q], hipEventDisableTiming) != hipSuccess) { partition_error_ref() = "event creation failed"; return 1; }
-    }
-    // this set's pages are read by the pass of the batch before last: the scatter stream waits for it (and a reallocation drains it)
-    if (ov.used[j] && hipStreamWaitEvent(s_scatter, ov.hist_done[j], 0) != hipSuccess) { partition_error_ref() = "stream wait failed"; return 1; }
-    {
-        const uint64_t nt = g.ntiles_all;
-        const uint32_t G = (uint32_t)(nt < g.Gmax ? nt : g.Gmax);
-        const uint32_t tpw = (uint32_t)((nt + G - 1) / G);
-        const size_t need = (size_t)G * scatter_wg_pages(tpw, g.rings, 512, g.tile_pos, 0);
-        if ((st.pages_cap < need || st.bkt_cap < (size_t)g.nb) && ov.used[j] && hipEventSynchronize(ov.hist_done[j]) != hipSuccess) { partition_error_ref() = "stream error"; return 1; }
-        const int rc = scatter_reserve_for(st, s_scatter, g, 0);
-        if (rc) return rc;
-        const size_t side_need = (size_t)g.Gmax * SC_HOT + 65536;
-        if (ov.side_cap < side_need) {
-            for (int q = 0; q < 2; q++) {
-                if (ov.side[q]) { if (ov.used[q] && hipEventSynchronize(ov.hist_done[q]) != hipSuccess) { partition_error_ref() = "stream error"; return 1; } (void)hipFree(ov.side[q]); ov.side[q] = nullptr; }
-                if (hipMalloc((void **)&ov.side[q], (2 + 2 * side_need) * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); ov.side_cap = 0; partition_error_ref() = "scratch allocation failed"; return 2; }
-            }
-            ov.side_cap = side_need;
-        }
-    }
-    hipLaunchKernelGGL(hot_side_kernel, dim3(1), dim3(1), 0, s_scatter, d_ctr, ov.side[j], (unsigned long long)ov.side_cap);
-    ScLaunch L;
-    if (scatter_stage1(st, s_scatter, g, 0, d_bases, nbytes, rs, k, canonical, 0, d_table, d_ctr, prof, &L)) return 1;
-    hipLaunchKernelGGL(hot_side_kernel, dim3(1), dim3(1), 0, s_scatter, d_ctr, (unsigned long long *)nullptr, 0ull);      // (whatever runs next on this stream adds directly again)
-    if (hipEventRecord(ov.scattered[j], s_scatter) != hipSuccess || hipStreamWaitEvent(s_hist, ov.scattered[j], 0) != hipSuccess) { partition_error_ref() = "stream error"; return 1; }
-    if (scatter_stage2(st, s_hist, g, L, d_table, d_ctr, prof)) return 1;
-    hipLaunchKernelGGL(apply_hot_kernel, dim3(8), dim3(256), 0, s_hist, (const unsigned long long *)ov.side[j], d_table);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ov.hist_done[j], s_hist) != hipSuccess) { partition_error_ref() = "paged scatter failed to launch"; return 1; }
-    ov.used[j] = true;
-    ov.last = j;
-    ov.next = j ^ 1;
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------
-// host: 13 <= k <= 17, two levels.   id = [ hi : 9 (k = 17: 10) ][ d1 : 2k - 24 (k = 17: 9) ][ d2 : 9 ][ lo : 6 ]
-//   level 1  scatter_bases_kernel   residues -> u32 remainders (id without d1), pages tagged d1
-//   level 2  scatter_ids_kernel     those pages -> u16 bins (hi | lo), pages tagged d1 << 9 | d2, into an ARENA that
-//                                   several batches share
-//   flush    one counting sort of the arena's tags, one page_hist_kernel: the sweep over the 4^k vector (8 GiB at
-//            k = 15, 128 GiB at k = 17: more than everything else in a batch) is paid once per <= PAGED_PENDING_MAX batches,
-//            at kdb_sync / kdb_finish, or when the arena is full -- not once per batch
-// ---------------------------------------------------------------------------------
-constexpr int PAGED_PENDING_MAX = 64;
-// a level-1 ring must take the arrivals of a round (8176 ids x ROUND / 16 / rings, spread evenly by the mid-bit digits) on
-// top of an incomplete line:
-constexpr int L1_RINGS = 256, L1_C = 64, L1_ROUND = 8;      // k <= 16 (<= 256 digits), u24 elements (64 KiB of LDS): 16 arrivals a round, two flush rounds per tile
-// k = 17 (512 digits), u32 elements (64 KiB): 8 arrivals a round on top of < 16 left over, two rounds per tile.  (Four rounds of 4 never
-// refuse an element but pay four barrier pairs: level 1 2.46-2.54 ms; two rounds repeat one for ~0.02 % of the rings: 2.09 ms.)
-constexpr int L1W_RINGS = 512, L1W_C = 32, L1W_ROUND = 8;
-// (128 rings x 128 elements with one round per tile: 2.30 ms as u32, 2.6-2.7 ms as u24 against 2.28 ms for 256 x 64 -- measured, k = 13..15)
-
-struct TwoLevelPaged {
-    ScatterState l1;                       // level-1 pages / tags / list (reused by every batch)
-    uint8_t *d_pages2 = nullptr; size_t cap2 = 0;      // the arena, in pages
-    uint32_t *d_tag2 = nullptr;
-    PageEntry *d_list2 = nullptr;
-    uint32_t *d_bkt2 = nullptr; size_t nb2_cap = 0;
-    uint32_t *d_wg_range = nullptr;        // [SC_GRID + 1] of the batch being scattered
-    size_t used2 = 0;                      // arena pages the pending batches can have taken at most (their worst cases added up)
-    // What they really took is only known on the device: l2_plan_kernel hands every batch the pages behind the previous one's
-    // last (d_cursor), not the host's worst case -- round 3 charged a fixed ~0.4 GiB per batch, four times the payload of a
-    // 64 MiB host-fed chunk.  The host learns the cursor by asynchronous read-backs (a few probes in flight, polled before
-    // every batch) and then only has to assume the worst for the batches behind the last probe that has landed.
-    static constexpr int PROBES = 8;
-    uint32_t *d_cursor = nullptr;
-    uint32_t *h_probe = nullptr;           // pinned [PROBES]
-    hipEvent_t ev_probe[PROBES] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t probe_bound[PROBES] = {0};      // used2 (worst cases added up) when the probe was sent
-    bool probe_live[PROBES] = {false};
-    int probe_next = 0;
-    size_t slack = 0;                      // used2 - slack = the host's present bound on the cursor
-    size_t tags_dirty = 0;                 // arena tags [0, tags_dirty) may have been written since they were last cleared
-    int pending = 0;                       // batches in the arena
-    int k_pending = 0;
-    int defer = 1;
-    size_t budget_bytes = 0;               // arena size; 0 = decide at first use (85 % of the free memory, less reserve_bytes)
-    int l1_one_round = 1;                  // 1: level 1 of k <= 15 (<= 64 leading digits) with 128 rings of 256 elements: one placement round per tile (engine option l1_one_round)
-    int l1_wide = 1;                       // 1: level 1 writes its pages in 128-byte pieces, one workgroup of 1024 threads per CU (engine option l1_wide_lines)
-    int l2_wide = 1;                       // 1: level 2 writes its pages in 128-byte pieces, one workgroup of 1024 threads per CU (engine option l2_wide_lines)
-    int l1k = 1;                           // 1: k = 15 (canonical, DROP) runs level 1's kernel compiled for that k; 0: the generic one (comparison)
-    size_t reserve_bytes = 0;              // device memory the arena must leave free whatever it grows to (RCCL's buffers and the reduce's scratch: kmerdb_amd/distributed.py)
-    size_t free_at_sizing = 0;             // what hipMemGetInfo reported when the budget was decided
-    bool table_is_zero = false;            // the engine cleared the vector and nothing has been added since
-    bool filled_up = false;                // the last flush came because the arena was full
-    bool grow_failed = false;              // a larger arena could not be allocated: no further attempts
-    uint64_t reallocs = 0;                 // (re)allocations of the arena so far
-    int grow = 1;                          // 0: the arena keeps its first size; 1: it doubles when that pays (below); 2: whenever it has filled up
-    uint64_t full_flushes = 0;             // flushes forced by a full arena since it got its present size
-    int first_batches = 8;                 // the arena's first size, in batches like the first one (engine option arena_batches)
-    uint64_t flushes = 0, flushed_batches = 0;     // histogram passes over the arena so far, and the batches they added to the vector
-};
-
-inline void twolevel_paged_free(TwoLevelPaged &tp)
-{
-    scatter_free(tp.l1);
-    if (tp.d_pages2) (void)hipFree(tp.d_pages2);
-    if (tp.d_tag2) (void)hipFree(tp.d_tag2);
-    if (tp.d_list2) (void)hipFree(tp.d_list2);
-    if (tp.d_bkt2) (void)hipFree(tp.d_bkt2);
-    if (tp.d_wg_range) (void)hipFree(tp.d_wg_range);
-    if (tp.d_cursor) (void)hipFree(tp.d_cursor);
-    if (tp.h_probe) (void)hipHostFree(tp.h_probe);
-    for (int i = 0; i < TwoLevelPaged::PROBES; i++) if (tp.ev_probe[i]) (void)hipEventDestroy(tp.ev_probe[i]);
-    const int defer = tp.defer, grow = tp.grow, first_batches = tp.first_batches, l1k = tp.l1k, l2_wide = tp.l2_wide, l1_wide = tp.l1_wide, l1_one_round = tp.l1_one_round;
-    const size_t budget = tp.budget_bytes, reserve = tp.reserve_bytes;
-    const ScatterState keep = tp.l1;
-    tp = TwoLevelPaged();
-    tp.defer = defer; tp.budget_bytes = budget; tp.reserve_bytes = reserve; tp.grow = grow; tp.first_batches = first_batches; tp.l1k = l1k; tp.l2_wide = l2_wide; tp.l1_wide = l1_wide; tp.l1_one_round = l1_one_round;
-    tp.l1.grid = keep.grid; tp.l1.lo_bits = keep.lo_bits; tp.l1.contig_pages = keep.contig_pages;
-}
-
-// kdb_reset / after a flush: no batch is pending any more (the cursor and the tags are cleared when the next cycle begins)
-inline void twolevel_paged_drop(TwoLevelPaged &tp)
-{
-    if (tp.used2 - tp.slack > tp.tags_dirty) tp.tags_dirty = tp.used2 - tp.slack;
-    tp.used2 = 0; tp.slack = 0; tp.pending = 0;
-    for (int i = 0; i < TwoLevelPaged::PROBES; i++) tp.probe_live[i] = false;
-}
-
-// what the device has told the host about the cursor so far: the newest probe that has landed decides
-inline void twolevel_paged_poll(TwoLevelPaged &tp)
-{
-    for (int i = 0; i < TwoLevelPaged::PROBES; i++) {
-        if (!tp.probe_live[i] || hipEventQuery(tp.ev_probe[i]) != hipSuccess) continue;
-        tp.probe_live[i] = false;
-        // the cursor stood at `actual` when the worst cases added up to probe_bound: every batch since adds at most its worst case to both
-        const size_t actual = tp.h_probe[i], bound = tp.probe_bound[i];
-        if (bound >= actual && bound - actual > tp.slack) tp.slack = bound - actual;
-    }
-    (void)hipGetLastError();               // (hipErrorNotReady of a probe still in flight is no error)
-}
-
-inline void paged_bits(int k, int *d1_bits, int *bin_bits)
-{
-    *bin_bits = k == 17 ? 16 : 15;
-    *d1_bits = 2 * k - *bin_bits - 9;                                   // 2, 4, 6, 8 (k = 13..16), 9 (k = 17)
-}
-
-// the histogram pass over everything in the arena
-inline int twolevel_paged_flush(TwoLevelPaged &tp, hipStream_t stream, unsigned long long *d_table, DevCounters *d_ctr, ProfHook &prof)
-{
-    if (tp.pending == 0) return 0;
-    const int k = tp.k_pending;
-    int d1, binb;
-    paged_bits(k, &d1, &binb);
-    const uint32_t nb2 = 1u << (d1 + 9);
-    const int table_is_zero = tp.table_is_zero ? 1 : 0;
-    tp.table_is_zero = false;
-    uint32_t *const bkt_pages = tp.d_bkt2, *const bkt_elems = tp.d_bkt2 + nb2, *const page_base = tp.d_bkt2 + 2 * (size_t)nb2,
-             *const slice_base = tp.d_bkt2 + 3 * (size_t)nb2 + 1;
-    twolevel_paged_poll(tp);
-    const uint32_t npages = (uint32_t)(tp.used2 - tp.slack);            // (an upper bound on the cursor: tags behind it say "no page")
-    if (npages == 0) {
-        // the device's cursor has told the host that the pending batches took no page at all (not one countable window among them: reads of
-        // N's in drop mode): nothing to sort, nothing to add -- and a launch with an empty grid is an error (found by tests/fuzz_gpu.py, round 4)
-        tp.flushes++; tp.flushed_batches += (uint64_t)tp.pending;
-        twolevel_paged_drop(tp);
-        return 0;
-    }
-    if (hipMemsetAsync(tp.d_bkt2, 0, 2 * (size_t)nb2 * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
-    prof.begin(KDB_KERNEL_PAGE_SORT);
-    const uint32_t pgrid = (npages + 4095u) / 4096u < 2048u ? (npages + 4095u) / 4096u : 2048u;     // (small chunks: few leading digits per LDS window)
-    uint32_t slice_pages = (npages + 2047u) / 2048u;
-    if (slice_pages < 128u) slice_pages = 128u;
-    hipLaunchKernelGGL(pages_count_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)tp.d_tag2, npages, nb2, bkt_pages, bkt_elems,
-                       &d_ctr->pages_ids, 32u);
-    hipLaunchKernelGGL(pages_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t *)bkt_pages, (const uint32_t *)bkt_elems, nb2, page_base, slice_base,
-                       slice_pages, (DevCounters *)nullptr);
-    hipLaunchKernelGGL(pages_place_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)tp.d_tag2, npages, nb2, bkt_pages,
-                       (const uint32_t *)page_base, tp.d_list2);
-    prof.end();
-    prof.begin(KDB_KERNEL_PAGE_HIST);
-    const uint32_t p2_grid = npages / slice_pages + nb2 + 1u;
-    const int lo_bits = tp.l1.lo_bits ? tp.l1.lo_bits : SC_LO_BITS_TWO_LEVEL, hi_shift = lo_bits + d1 + 9;
-    if (binb == 16)
-        hipLaunchKernelGGL(page_hist_kernel<true>, dim3(p2_grid), dim3(P2_THREADS), 0, stream, (const uint8_t *)tp.d_pages2, (const PageEntry *)tp.d_list2,
-                           (const uint32_t *)page_base, (const uint32_t *)slice_base, nb2, d_table, lo_bits, hi_shift, table_is_zero, d_ctr);
-    else
-        hipLaunchKernelGGL(page_hist_kernel<false>, dim3(p2_grid), dim3(P2_THREADS), 0, stream, (const uint8_t *)tp.d_pages2, (const PageEntry *)tp.d_list2,
-                           (const uint32_t *)page_base, (const uint32_t *)slice_base, nb2, d_table, lo_bits, hi_shift, table_is_zero, d_ctr);
-    prof.end();
-    tp.flushes++; tp.flushed_batches += (uint64_t)tp.pending;
-    twolevel_paged_drop(tp);
-    if (hipGetLastError() != hipSuccess) { partition_error_ref() = "histogram pass over the page arena failed to launch"; return 1; }
-    return 0;
-}
-
-// returns 0 ok, 1 error (partition_error()), 2 no room for the scratch (nothing of the batch was counted)
-inline int twolevel_paged_count(TwoLevelPaged &tp, hipStream_t stream, const uint8_t *d_bases, size_t nbytes, const RecStarts &rs,
-                                size_t max_windows /* nbytes - records x (k - 1) */,
-                                int k, int canonical, int n_expand, unsigned long long *d_table, DevCounters *d_ctr, ProfHook &prof)
-{
-    int d1, binb;
-    paged_bits(k, &d1, &binb);
-    const int nb1 = 1 << d1;
-    const uint32_t nb2 = 1u << (d1 + 9);
-    const bool wide = k == 17;
-    const int lo_bits = tp.l1.lo_bits ? tp.l1.lo_bits : SC_LO_BITS_TWO_LEVEL;
-    // k <= 15 (option l1_one_round): 128 rings of 256 three-byte elements instead of 256 of 128 -- a ring then takes a whole tile's arrivals (128 +- 34 on top of < 64
-    // left over) and the tile is placed in ONE round: two barriers and one flush per tile instead of four and two; level 1 1.82 -> 1.67 ms at k = 15 (the 64 lanes of a
-    // request meet in 128 rings more often than in 256: not the 30 % the instruction count promised).  k = 16 has 256 digits: 256 rings of 256 elements do not fit.
-    const bool one_round1 = tp.l1_one_round != 0 && tp.l1_wide != 0 && !wide && (1 << d1) <= 128;
-    const int rings1 = wide ? L1W_RINGS : (one_round1 ? 128 : L1_RINGS);
-    // level-1 elements: 24-bit remainders in three bytes (k <= 16), 25-bit ones in four (k = 17)
-    const uint32_t l1_page_elems = wide ? 256u : 512u;
-    const size_t l1_page_bytes = wide ? (size_t)ElemFmt<uint32_t>::PAGE_BYTES : (size_t)ElemFmt<u24>::PAGE_BYTES;
-    int sub_log2 = 0;
-    while ((nb1 << sub_log2) < rings1) sub_log2++;
-    // level 1 in 128-byte pieces (option l1_wide_lines): one workgroup of 1024 threads per CU, rings of twice the elements, tiles of 1023 chunks
-    const bool wide1 = tp.l1_wide != 0;
-    const uint32_t tile_stride1 = wide1 ? (uint32_t)SC1_THREADS - 1u : (uint32_t)SC_TILE_STRIDE, tile_pos1 = tile_stride1 * 16u;
-    const uint64_t ntiles_all = ((nbytes + 15) / 16 + tile_stride1 - 1) / tile_stride1;
-    const uint32_t Gmax = tp.l1.grid > 0 ? (uint32_t)tp.l1.grid : (uint32_t)(wide1 ? SC1_GRID : SC_GRID);
-    const uint64_t max_tiles = scatter_max_tiles(Gmax, tile_pos1);
-    if (tp.pending && tp.k_pending != k) { if (twolevel_paged_flush(tp, stream, d_table, d_ctr, prof)) return 1; }
-    // level-1 scratch for the largest sub-batch; small arrays
-    {
-        const uint64_t nt = ntiles_all < max_tiles ? ntiles_all : max_tiles;
-        const uint32_t G = (uint32_t)(nt < Gmax ? nt : Gmax);
-        const uint32_t tpw = (uint32_t)((nt + G - 1) / G);
-        const int rc = scatter_reserve(tp.l1, stream, (size_t)G * scatter_wg_pages(tpw, rings1, l1_page_elems, tile_pos1, scatter_extra_elems(tpw, tile_pos1, n_expand)),
-                                       (size_t)nb1, l1_page_bytes);
-        if (rc == 2) { partition_error_ref() = "scratch allocation failed"; return 2; }
-        if (rc) { partition_error_ref() = "stream error"; return 1; }
-    }
-    if (!tp.d_wg_range && hipMalloc((void **)&tp.d_wg_range, (SC_GRID + 1) * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); partition_error_ref() = "scratch allocation failed"; return 2; }
-    if (!tp.d_cursor) {
-        if (hipMalloc((void **)&tp.d_cursor, sizeof(uint32_t)) != hipSuccess ||
-            hipHostMalloc((void **)&tp.h_probe, TwoLevelPaged::PROBES * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); partition_error_ref() = "scratch allocation failed"; return 2; }
-        for (int i = 0; i < TwoLevelPaged::PROBES; i++)
-            if (hipEventCreateWithFlags(&tp.ev_probe[i], hipEventDisableTiming) != hipSuccess) { partition_error_ref() = "event creation failed"; return 1; }
-    }
-    if (tp.nb2_cap < nb2) {
-        if (tp.d_bkt2) { if (hipStreamSynchronize(stream) != hipSuccess) return 1; (void)hipFree(tp.d_bkt2); tp.d_bkt2 = nullptr; tp.nb2_cap = 0; }
-        if (hipMalloc((void **)&tp.d_bkt2, (4 * (size_t)nb2 + 2) * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); partition_error_ref() = "scratch allocation failed"; return 2; }
-        tp.nb2_cap = nb2;
-    }
-    uint32_t *const bkt_pages1 = tp.l1.d_bkt, *const bkt_elems1 = tp.l1.d_bkt + nb1, *const page_base1 = tp.l1.d_bkt + 2 * nb1, *const slice_base1 = tp.l1.d_bkt + 3 * nb1 + 1;
-    for (uint64_t t0 = 0; t0 < ntiles_all; t0 += max_tiles) {
-        const uint32_t nt = (uint32_t)((ntiles_all - t0) < max_tiles ? (ntiles_all - t0) : max_tiles);
-        const uint32_t G = nt < Gmax ? nt : Gmax;
-        ScOut out1;
-        out1.pages = tp.l1.d_pages; out1.tag = tp.l1.d_tag; out1.wg_range = nullptr; out1.contig = (uint32_t)tp.l1.contig_pages; out1.wg_base = 0; out1.grid = 0;
-        out1.extra_elems = scatter_extra_elems((nt + G - 1) / G, tile_pos1, n_expand);
-        out1.wg_pages = scatter_wg_pages((nt + G - 1) / G, rings1, l1_page_elems, tile_pos1, out1.extra_elems);
-        const uint32_t npages1 = G * out1.wg_pages;
-        // what level 2 can need at most (l2_plan_kernel hands out exactly what it does need, within this)
-        const bool wide2 = tp.l2_wide != 0;                               // level 2 in 128-byte pieces: one workgroup of 1024 threads per CU
-        const uint32_t G2 = wide2 ? (uint32_t)SC1_GRID : (uint32_t)SC_GRID;
-        // (a page per 512 of the elements level 1 can emit -- at most one per position, N expansions go straight to the vector --
-        //  plus level 1's partial pages rounded up, plus a partial page per ring and digit span of every level-2 workgroup)
-        //  A batch of records that are all at least k long has nbytes - records x (k - 1) windows; one that is not fails at the
-        //  sync, and until then a scatter kernel that runs out of its page sequence stops writing (internal_err), never out of bounds.
-        // (N-expansion mode: plus the fills of N-windows that level 1 may send through its rings)
-        const size_t pos = (size_t)nt * tile_pos1, elems = (pos < max_windows ? pos : max_windows) + (size_t)G * out1.extra_elems;
-        const size_t need2 = (elems + 511) / 512 + (size_t)G * (size_t)rings1 + 2 * (size_t)G2 + 512 * ((size_t)nb1 + G2) + 16;
-        // room in the arena (acquired before any kernel of the sub-batch runs: "no room" must leave nothing counted)
-        if (tp.budget_bytes == 0) {
-            size_t free_b = 0, total_b = 0;
-            (void)hipMemGetInfo(&free_b, &total_b);
-            // 85 % of what is free now (the vector and level 1's scratch are allocated already): every batch more in the arena
-            // makes the sweep of the 4^k vector cheaper per batch (k = 17: 61 ms per flush, 24 batches at 70 % -> 2.5 ms each)
-            tp.free_at_sizing = free_b;
-            tp.budget_bytes = free_b / 100 * 85;
-            // (a job that ends in a reduce: RCCL allocates its channel and peer-to-peer buffers at the first collective of each kind, and the
-            //  sharded reduce shapes want a chunk of scratch -- the arena, which sizes itself on what is free, must not have taken that room)
-            if (tp.reserve_bytes && tp.budget_bytes + tp.reserve_bytes > free_b) tp.budget_bytes = free_b > tp.reserve_bytes ? free_b - tp.reserve_bytes : 0;
-            if (tp.budget_bytes > (192ull << 30)) tp.budget_bytes = 192ull << 30;
-            if (tp.budget_bytes < (1ull << 30)) tp.budget_bytes = 1ull << 30;
-        }
-        size_t budget_pages = tp.defer ? tp.budget_bytes / SC_PAGE_BYTES : 0;
-        if (tp.grow_failed && budget_pages > tp.cap2) budget_pages = tp.cap2;       // (a larger arena could not be had: what there is, is the budget)
-        if (budget_pages < need2) budget_pages = need2;
-        // worth enlarging: the arena filled up, a quarter more (at least) is within the budget -- and the larger arena pays.
-        // Fresh device memory costs ~46 ms per GiB on this runtime (hipMalloc of 128 GiB: 5.9 s, tools/malloc_time.py); a flush
-        // forced by a full arena costs one sweep of the vector (16 B per counter at ~5.5 TB/s: 50 ms at k = 17, 3 ms at k = 15),
-        // and twice the arena saves every second one.  The arena doubles once the sweeps it would have saved so far add up to
-        // the price of the allocation (so a job never spends more than about twice what the best fixed size would have cost
-        // it): k = 17 after ~90 forced flushes at 8 batches per flush, k <= 15 in effect never.
-        bool may_grow = tp.filled_up && tp.cap2 + tp.cap2 / 4 <= budget_pages && tp.grow != 0;
-        if (may_grow && tp.grow == 1) {
-            const size_t next_cap = 2 * tp.cap2 < budget_pages ? 2 * tp.cap2 : budget_pages;
-            const double alloc_ms = (double)next_cap * (double)SC_PAGE_BYTES / (double)(1ull << 30) * 46.0;
-            const double sweep_ms = (double)(1ull << (2 * k)) * 16.0 / 5.5e9;
-            may_grow = (double)tp.full_flushes * sweep_ms * 0.5 >= alloc_ms;
-        }
-        twolevel_paged_poll(tp);
-        if (tp.used2 - tp.slack + need2 > tp.cap2 || tp.cap2 == 0 || may_grow) {
-            if (tp.pending) { if (twolevel_paged_flush(tp, stream, d_table, d_ctr, prof)) return 1; }
-            tp.filled_up = false;
-            // The arena grows with the job: room for eight batches like this one at first, twice as much every time it has
-            // filled up, until the budget is reached -- a small job (or several processes on one device) never holds tens
-            // of GiB it does not use, a long one amortises the sweep of the vector over as many batches as fit.
-            size_t want_cap = tp.cap2 == 0 ? (size_t)tp.first_batches * need2 : 2 * tp.cap2;
-            if (want_cap > budget_pages) want_cap = budget_pages;
-            if (want_cap < need2) want_cap = need2;
-            if (tp.cap2 < need2 || (may_grow && tp.cap2 < want_cap) || tp.cap2 == 0) {
-                if (hipStreamSynchronize(stream) != hipSuccess) return 1;
-                const size_t old_cap = tp.cap2;
-                if (tp.d_pages2) { (void)hipFree(tp.d_pages2); (void)hipFree(tp.d_tag2); (void)hipFree(tp.d_list2); tp.d_pages2 = nullptr; tp.d_tag2 = nullptr; tp.d_list2 = nullptr; tp.cap2 = 0; }
-                // what is wanted; failing that what there was (and no further attempts to grow); failing that just this batch
-                const size_t tries[3] = {want_cap, old_cap >= need2 ? old_cap : need2, need2};
-                for (int attempt = 0; attempt < 3 && !tp.d_pages2; attempt++) {
-                    const size_t cap = tries[attempt];
-                    if (attempt && cap == tries[attempt - 1]) continue;
-                    if (hipMalloc((void **)&tp.d_pages2, cap * (size_t)SC_PAGE_BYTES) == hipSuccess &&
-                        hipMalloc((void **)&tp.d_tag2, cap * sizeof(uint32_t)) == hipSuccess &&
-                        hipMalloc((void **)&tp.d_list2, cap * sizeof(PageEntry)) == hipSuccess) { tp.cap2 = cap; tp.tags_dirty = cap; if (attempt) tp.grow_failed = true; break; }
-                    (void)hipGetLastError();
-                    if (tp.d_pages2) (void)hipFree(tp.d_pages2);
-                    if (tp.d_tag2) (void)hipFree(tp.d_tag2);
-                    if (tp.d_list2) (void)hipFree(tp.d_list2);
-                    tp.d_pages2 = nullptr; tp.d_tag2 = nullptr; tp.d_list2 = nullptr;
-                }
-                tp.reallocs++;
-                tp.full_flushes = 0;
-                if (!tp.d_pages2) { partition_error_ref() = "scratch allocation failed"; return t0 == 0 ? 2 : 1; }
-            }
-        }
-        if (tp.pending == 0) {
-            // a new cycle: the cursor goes back to the start of the arena, and the tags the last cycle (or a fresh allocation) left behind are cleared
-            if (tp.tags_dirty > tp.cap2) tp.tags_dirty = tp.cap2;
-            if (hipMemsetAsync(tp.d_cursor, 0, sizeof(uint32_t), stream) != hipSuccess ||
-                (tp.tags_dirty && hipMemsetAsync(tp.d_tag2, 0xFF, tp.tags_dirty * sizeof(uint32_t), stream) != hipSuccess)) { partition_error_ref() = "memset failed"; return 1; }
-            tp.tags_dirty = 0;
-        }
-        if (hipMemsetAsync(tp.l1.d_tag, 0xFF, (size_t)npages1 * sizeof(uint32_t), stream) != hipSuccess ||
-            hipMemsetAsync(tp.l1.d_bkt, 0, 2 * (size_t)nb1 * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
-        // ---- level 1
-        prof.begin(KDB_KERNEL_SCATTER);
-#define KDB_LAUNCH_L1K(ID, EL, RG, CC, RD, TH, E, CN, RAG, KK)                                                                                 \
-    hipLaunchKernelGGL((scatter_bases_kernel<ID, EL, RG, CC, RD, E, CN, KK, TH, RAG>), dim3(G), dim3(TH), 0, stream, d_bases,                 \
-                       (uint64_t)nbytes, (uint32_t)t0, nt, k, lo_bits + 9, d1, sub_log2, out1, d_table, d_ctr, rs)
-#define KDB_LAUNCH_L1R(ID, EL, RG, CC, RD, TH, E, CN, RAG) KDB_LAUNCH_L1K(ID, EL, RG, CC, RD, TH, E, CN, RAG, 0)
-#define KDB_LAUNCH_L1(ID, EL, RG, CC, RD, TH, E, CN) do { KDB_LAUNCH_L1R(ID, EL, RG, CC, RD, TH, E, CN, false); KDB_LAUNCH_L1R(ID, EL, RG, CC, RD, TH, E, CN, true); } while (0)
-#define KDB_LAUNCH_L1_MODES(ID, EL, RG, CC, RD, TH)                                                                                            \
-    do {                                                                                                                                       \
-        if (n_expand) { if (canonical) KDB_LAUNCH_L1(ID, EL, RG, CC, RD, TH, true, true); else KDB_LAUNCH_L1(ID, EL, RG, CC, RD, TH, true, false); }     \
-        else          { if (canonical) KDB_LAUNCH_L1(ID, EL, RG, CC, RD, TH, false, true); else KDB_LAUNCH_L1(ID, EL, RG, CC, RD, TH, false, false); }   \
-    } while (0)
-        const bool compiled15 = !wide && k == 15 && !n_expand && canonical && lo_bits == SC_LO_BITS_TWO_LEVEL && tp.l1k;
-        const bool compiled17 = wide && wide1 && !n_expand && canonical && lo_bits == SC_LO_BITS_TWO_LEVEL && tp.l1k;      // BASELINE config 4's level 1, likewise
-        // (k = 14 and k = 16 likewise, canonical drop mode: the kernels of the default path)
-        const bool compiled14 = !wide && k == 14 && !n_expand && canonical && lo_bits == SC_LO_BITS_TWO_LEVEL && tp.l1k;
-        const bool compiled16 = !wide && k == 16 && !n_expand && canonical && lo_bits == SC_LO_BITS_TWO_LEVEL && tp.l1k;
-        if (one_round1) {
-            if (compiled15) {
-                KDB_LAUNCH_L1K(uint32_t, u24w, 128, 256, 16, SC1_THREADS, false, true, false, 15);
-                KDB_LAUNCH_L1K(uint32_t, u24w, 128, 256, 16, SC1_THREADS, false, true, true, 15);
-            } else if (compiled14) {
-                KDB_LAUNCH_L1K(uint32_t, u24w, 128, 256, 16, SC1_THREADS, false, true, false, 14);
-                KDB_LAUNCH_L1K(uint32_t, u24w, 128, 256, 16, SC1_THREADS, false, true, true, 14);
-            } else KDB_LAUNCH_L1_MODES(uint32_t, u24w, 128, 256, 16, SC1_THREADS);
-        } else if (wide1 && compiled16) {
-            KDB_LAUNCH_L1K(uint32_t, u24w, L1_RINGS, 2 * L1_C, L1_ROUND, SC1_THREADS, false, true, false, 16);
-            KDB_LAUNCH_L1K(uint32_t, u24w, L1_RINGS, 2 * L1_C, L1_ROUND, SC1_THREADS, false, true, true, 16);
-        } else if (wide1) {
-            if (compiled15) {
-                KDB_LAUNCH_L1K(uint32_t, u24w, L1_RINGS, 2 * L1_C, L1_ROUND, SC1_THREADS, false, true, false, 15);
-                KDB_LAUNCH_L1K(uint32_t, u24w, L1_RINGS, 2 * L1_C, L1_ROUND, SC1_THREADS, false, true, true, 15);
-            } else if (!wide) KDB_LAUNCH_L1_MODES(uint32_t, u24w, L1_RINGS, 2 * L1_C, L1_ROUND, SC1_THREADS);
-            else if (compiled17) {
-                KDB_LAUNCH_L1K(uint64_t, u32w, L1W_RINGS, 2 * L1W_C, L1W_ROUND, SC1_THREADS, false, true, false, 17);
-                KDB_LAUNCH_L1K(uint64_t, u32w, L1W_RINGS, 2 * L1W_C, L1W_ROUND, SC1_THREADS, false, true, true, 17);
-            }
-            else KDB_LAUNCH_L1_MODES(uint64_t, u32w, L1W_RINGS, 2 * L1W_C, L1W_ROUND, SC1_THREADS);
-        } else if (compiled15) {
-            // BASELINE config 3's kernel with its shifts and masks compiled in (as the k = 12 headline's)
-            KDB_LAUNCH_L1K(uint32_t, u24, L1_RINGS, L1_C, L1_ROUND, SC_THREADS, false, true, false, 15);
-            KDB_LAUNCH_L1K(uint32_t, u24, L1_RINGS, L1_C, L1_ROUND, SC_THREADS, false, true, true, 15);
-        } else if (!wide) KDB_LAUNCH_L1_MODES(uint32_t, u24, L1_RINGS, L1_C, L1_ROUND, SC_THREADS);
-        else KDB_LAUNCH_L1_MODES(uint64_t, uint32_t, L1W_RINGS, L1W_C, L1W_ROUND, SC_THREADS);
-#undef KDB_LAUNCH_L1_MODES
-#undef KDB_LAUNCH_L1
-#undef KDB_LAUNCH_L1R
-#undef KDB_LAUNCH_L1K
-        prof.end();
-        prof.begin(KDB_KERNEL_PAGE_SORT);
-        const uint32_t pgrid = (npages1 + 4095u) / 4096u < 256u ? (npages1 + 4095u) / 4096u : 256u;
-        hipLaunchKernelGGL(pages_count_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)tp.l1.d_tag, npages1, (uint32_t)nb1, bkt_pages1, bkt_elems1,
-                           &d_ctr->pages_bases, wide ? 16u : 32u);
-        hipLaunchKernelGGL(pages_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t *)bkt_pages1, (const uint32_t *)bkt_elems1, (uint32_t)nb1, page_base1,
-                           slice_base1, 1u << 20, d_ctr);
-        hipLaunchKernelGGL(pages_place_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)tp.l1.d_tag, npages1, (uint32_t)nb1, bkt_pages1,
-                           (const uint32_t *)page_base1, tp.l1.d_list);
-        hipLaunchKernelGGL(l2_plan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t *)page_base1, (uint32_t)nb1, G2, 512u, l1_page_elems, tp.d_wg_range, tp.d_cursor,
-                           (uint32_t)tp.cap2, d_ctr);
-        prof.end();
-        tp.used2 += need2;
-        {
-            // tell the host where the cursor stands now (a probe slot that is still in flight is left alone: the bound stays valid without it)
-            const int pi = tp.probe_next;
-            if (!tp.probe_live[pi] && hipMemcpyAsync(&tp.h_probe[pi], tp.d_cursor, sizeof(uint32_t), hipMemcpyDeviceToHost, stream) == hipSuccess &&
-                hipEventRecord(tp.ev_probe[pi], stream) == hipSuccess) {
-                tp.probe_live[pi] = true; tp.probe_bound[pi] = tp.used2;
-                tp.probe_next = (pi + 1) % TwoLevelPaged::PROBES;
-            }
-        }
-        // ---- level 2
-        ScOut out2;
-        out2.pages = tp.d_pages2; out2.tag = tp.d_tag2; out2.wg_pages = 0; out2.wg_range = tp.d_wg_range; out2.contig = 0; out2.wg_base = 0; out2.grid = 0; out2.extra_elems = 0;
-        prof.begin(KDB_KERNEL_SCATTER_L2);
-#define KDB_LAUNCH_L2(IN, EL, CC, FX, TH)                                                                                                       \
-    hipLaunchKernelGGL((scatter_ids_kernel<IN, EL, 512, CC, FX, TH>), dim3(G2), dim3(TH), 0, stream, (const uint8_t *)tp.l1.d_pages,            \
-                       (const PageEntry *)tp.l1.d_list, (const uint32_t *)page_base1, (uint32_t)nb1, lo_bits, 9, out2, d_ctr)
-        const bool fixed2 = lo_bits == SC_LO_BITS_TWO_LEVEL && tp.l1k;   // (shifts and masks compiled in)
-        if (wide2) {
-            if (wide && fixed2) KDB_LAUNCH_L2(uint32_t, u16w, 128, true, SC1_THREADS);
-            else if (wide) KDB_LAUNCH_L2(uint32_t, u16w, 128, false, SC1_THREADS);
-            else if (fixed2) KDB_LAUNCH_L2(u24, u16w, 128, true, SC1_THREADS);
-            else KDB_LAUNCH_L2(u24, u16w, 128, false, SC1_THREADS);
-        } else {
-            if (wide) KDB_LAUNCH_L2(uint32_t, uint16_t, 64, false, SC_THREADS);
-            else if (fixed2) KDB_LAUNCH_L2(u24, uint16_t, 64, true, SC_THREADS);
-            else KDB_LAUNCH_L2(u24, uint16_t, 64, false, SC_THREADS);
-        }
-#undef KDB_LAUNCH_L2
-        prof.end();
-        tp.pending++;
-        tp.k_pending = k;
-        if (hipGetLastError() != hipSuccess) { partition_error_ref() = "two-level paged scatter failed to launch"; return 1; }
-        // flush now if told not to defer, after PAGED_PENDING_MAX batches, or when another batch like this one would not fit the arena
-        if (tp.defer && tp.used2 - tp.slack + need2 > tp.cap2) { tp.filled_up = true; tp.full_flushes++; }      // (the next batch finds the arena empty and may enlarge it)
-        if (!tp.defer || tp.pending >= PAGED_PENDING_MAX || tp.used2 - tp.slack + need2 > tp.cap2) { if (twolevel_paged_flush(tp, stream, d_table, d_ctr, prof)) return 1; }
-    }
-    return 0;
-}
-
 }  // namespace kdb

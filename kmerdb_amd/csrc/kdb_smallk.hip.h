@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "kdb_scatter.hip.h"
+#include "kdb_scatter_host.hip.h"
 
 namespace kdb {
 

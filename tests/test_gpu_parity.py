@@ -1467,3 +1467,58 @@ def test_hbm_pattern_probe_reports_every_pattern(gpu_engine_cls):
     assert gbs["scatter_128"] > gbs["scatter_64"] and gbs["level2_128"] > gbs["level2_64"], gbs
     with pytest.raises(ValueError):
         kmerdb_amd._abi.check(L.kdb_hbm_pattern_probe(0, out, n - 1))
+
+
+SETTABLE_OPTIONS = {          # name: a value it accepts
+    "algo": 2, "defer_flush": 1, "pending_budget": 0, "l1_compiled_k": 1, "l1_wide_lines": 1, "l1_one_round": 1, "l2_wide_lines": 1, "reserve_bytes": 0,
+    "arena_grow": 1, "smallk_old": 0, "one_level_max_k": 13, "arena_batches": 8, "sc_grid": 0, "overlap": 0, "overlap_hist_cus": 0, "overlap_mask_mode": 0,
+    "sc_lo_bits": 0, "sc_top_bits": 0, "sc_contig_pages": 1, "sc_wide_lines": 1, "accum_bytes": -1, "stage_bytes": 64 << 20, "min_len": 0, "copy_threads": 8,
+    "stage_reads": 2 << 20}
+READABLE_OPTIONS = (
+    "algo", "reserve_bytes", "arena_budget_bytes", "free_at_sizing", "free_hbm", "overlap", "overlap_hist_cus", "overlap_scatter_grid", "stage_bytes", "stage_reads",
+    "k", "defer_flush", "sc_lo_bits", "sc_contig_pages", "sc_wide_lines", "l1_wide_lines", "l2_wide_lines", "l1_one_round", "oom_fallbacks", "pending_batches",
+    "d2h_bytes", "folded_files", "bytes_in", "arena_pages", "arena_used_bound", "arena_worst_case", "arena_cursor", "arena_reallocs", "arena_grow", "arena_batches",
+    "one_level_max_k", "smallk_old", "hist_flushes", "flushed_batches", "full_flushes",
+    "pages_bases", "lines_bases", "pages_ids", "lines_ids", "table_bytes", "total_kmers")          # (the six device counters)
+BOOLEAN_OPTIONS_WITH_A_GETTER = ("defer_flush", "l1_wide_lines", "l1_one_round", "l2_wide_lines", "smallk_old", "overlap", "sc_contig_pages", "sc_wide_lines")
+REFUSED_VALUES = (("algo", 4), ("arena_grow", 3), ("one_level_max_k", 11), ("arena_batches", 0), ("arena_batches", 65), ("sc_grid", 1025), ("sc_lo_bits", 16),
+                  ("accum_bytes", -2), ("stage_bytes", 4095), ("stage_bytes", 4104), ("min_len", 65), ("copy_threads", 0), ("stage_reads", 0),
+                  ("pending_budget", -1), ("reserve_bytes", -1), ("overlap", 1025))
+
+
+def test_every_engine_option_keeps_its_name_its_range_and_its_lock(gpu_engine_cls):
+    """What kdb_set_option / kdb_get_option accept: the 25 settable and 41 readable names, booleans normalised to 0 / 1, the sc_top_bits alias,
+    the values each option refuses, and the staging options locked once a host submit has allocated the staging buffers."""
+    import kmerdb_amd
+    assert len(SETTABLE_OPTIONS) == 25 and len(READABLE_OPTIONS) == 41
+    with gpu_engine_cls(9) as eng:
+        for name, value in SETTABLE_OPTIONS.items():
+            eng.set_option(name, value)
+        for name in READABLE_OPTIONS:
+            assert isinstance(eng.get_option(name), int), name
+        assert eng.get_option("k") == 9
+        with pytest.raises(ValueError):
+            eng.set_option("no_such_option", 1)
+        with pytest.raises(ValueError):
+            eng.get_option("no_such_option")
+        for name in BOOLEAN_OPTIONS_WITH_A_GETTER:
+            before = eng.get_option(name)
+            eng.set_option(name, 5)
+            assert eng.get_option(name) == 1, name
+            eng.set_option(name, 0)
+            assert eng.get_option(name) == 0, name
+            eng.set_option(name, before)
+        eng.set_option("sc_top_bits", 1)
+        assert eng.get_option("sc_lo_bits") == 15
+        eng.set_option("sc_top_bits", 0)
+        assert eng.get_option("sc_lo_bits") == 0
+        for name, value in REFUSED_VALUES:
+            with pytest.raises(ValueError) as info:
+                eng.set_option(name, value)
+            assert name in str(info.value) and str(value) in str(info.value), (name, value, str(info.value))
+        read = np.frombuffer(b"ACGTTGCAACGTAGGCTTAC", dtype=np.uint8)
+        eng.submit(read, np.array([0, read.size], dtype=np.uint64))
+        for name in ("stage_bytes", "stage_reads", "accum_bytes"):
+            with pytest.raises(kmerdb_amd._abi.KdbHipError):
+                eng.set_option(name, SETTABLE_OPTIONS[name])
+        eng.sync()

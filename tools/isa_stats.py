@@ -1,6 +1,7 @@
 """Per-kernel instruction statistics of a `hipcc -save-temps` assembly file (gfx950): VALU / v_mov / LDS / waits on lgkmcnt(0), registers, scratch.
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -I include -save-temps -o /tmp/isa/lib.so kmerdb_amd/csrc/kdb_engine.hip
     python tools/isa_stats.py /tmp/isa/kdb_engine-hip-amdgcn-amd-amdhsa-gfx950.s [substring ...]
+    python tools/isa_stats.py --diff A.s B.s          (are the kernels of two builds the same, name for name and line for line?)
 A returning LDS atomic followed at once by `s_waitcnt lgkmcnt(0)`, or dozens of v_mov per atomic, is how round 4 found the histogram adds
 the compiler had serialised."""
 import re
@@ -8,8 +9,8 @@ import subprocess
 import sys
 
 
-def kernel_stats(path):
-    """-> {demangled kernel name: {insts, valu, v_mov, salu, ds, ds_rtn_atomics, vmem, waits_lgkmcnt0, barriers, vgprs, scratch, occupancy, lds}}"""
+def kernel_bodies(path):
+    """-> {mangled kernel name: the lines behind its label}, for the functions that end a program"""
     funcs, cur = {}, None
     for line in open(path):
         m = re.match(r'^(_Z\w+):', line)
@@ -18,7 +19,13 @@ def kernel_stats(path):
             funcs[cur] = []
         elif cur is not None:
             funcs[cur].append(line.rstrip("\n"))
-    names = [n for n, b in funcs.items() if any('s_endpgm' in x for x in b)]
+    return {n: b for n, b in funcs.items() if any('s_endpgm' in x for x in b)}
+
+
+def kernel_stats(path):
+    """-> {demangled kernel name: {insts, valu, v_mov, salu, ds, ds_rtn_atomics, vmem, waits_lgkmcnt0, barriers, vgprs, scratch, occupancy, lds}}"""
+    funcs = kernel_bodies(path)
+    names = list(funcs)
     dem = subprocess.run(['c++filt'], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
     out = {}
     for n, d in zip(names, dem):
@@ -34,7 +41,27 @@ def kernel_stats(path):
     return out
 
 
+def diff(path_a, path_b):
+    """Compare two builds kernel by kernel.  A kernel's local labels carry its position in the file (.LBB<n>_, BB<n>_ in comments, .Lfunc_end<n>): the position is
+    masked, so that kernels emitted in another order still compare equal; lines that name the per-build __hip_cuid_ symbol are left out."""
+    def norm(body):
+        end = body.index("; Kernel info:")          # the kernel ends with this block of comments: behind it the next function is announced
+        while end < len(body) and body[end].startswith(";"):
+            end += 1
+        return [re.sub(r'(BB|Lfunc_end|Lfunc_begin)\d+', r'\1#', x) for x in body[:end] if '__hip_cuid_' not in x]
+    a, b = kernel_bodies(path_a), kernel_bodies(path_b)
+    only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
+    differ = [n for n in a if n in b and norm(a[n]) != norm(b[n])]
+    print("kernels: %d in A, %d in B; only in A: %d, only in B: %d; in both but different: %d" % (len(a), len(b), len(only_a), len(only_b), len(differ)))
+    for tag, names in (("only in A", only_a), ("only in B", only_b), ("different", differ)):
+        for n in names:
+            print("  %s: %s" % (tag, n[:200]))
+    return 1 if only_a or only_b or differ else 0
+
+
 def main():
+    if sys.argv[1] == "--diff":
+        sys.exit(diff(sys.argv[2], sys.argv[3]))
     path, pats = sys.argv[1], sys.argv[2:]
     for d, v in kernel_stats(path).items():
         if pats and not any(p in d for p in pats):
