@@ -459,7 +459,7 @@ def _table_checksum(t):
 @pytest.mark.gpu
 @pytest.mark.parametrize("k", [13, 15, 16])            # (k = 17: test_k17_bins_counted_more_than_65535_times_in_one_flush and config 4's tests run deferred passes over its 128 GiB vector)
 def test_deferred_histogram_pass_over_many_batches(gpu_engine_cls, oracle, k):
-    """k >= 14: batches are partitioned as they come and added to the vector together (at sync, or after 16 batches).
+    """k >= 14: batches are partitioned as they come and added to the vector together (at sync, or after 64 batches).
     The result must not depend on how many batches were pending, on reset() dropping them, or on the option."""
     from kmerdb_amd import synth
     import torch
