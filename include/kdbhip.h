@@ -163,6 +163,26 @@ int kdb_nullomers(kdb_engine *e, int folded, uint64_t *ids_out, uint64_t cap, ui
 int kdb_reduce(kdb_engine *const *engines, int n, int root);
 
 /*
+ * Exact integer moments of n finished count vectors on one device, in one sweep (csrc/kdb_gram.hip.h): what every distance of
+ * `kmerdb distance` on count profiles is a function of (kmerdb/__init__.py:577-813, distance.pyx:108-152; kmerdb_amd/distance.py).
+ *   S[i]    = Sum_b x_i[b]            -> sums_out[2 i], [2 i + 1] = low, high 64 bits
+ *   G[i][j] = Sum_b x_i[b] x_j[b]     -> gram_out[2 (i n + j)], [.. + 1]; both triangles are filled
+ * d_vectors: n device pointers (a host array of them) to nbins uint64 each, 16-byte aligned, read only; the same pointer may appear
+ * twice.  Synchronous; the caller has synchronised whatever produced the vectors; scratch is allocated and freed inside the call.
+ * If every S[i] < 2^64 then G[i][j] <= S[i] S[j] < 2^128: 128-bit accumulation cannot wrap.  KDB_ERR_ARG: n < 1, n > KDB_GRAM_MAX,
+ * nbins == 0 (or above 2^36: no device holds such a vector), a NULL or misaligned pointer, or some S[i] >= 2^64 (the sums are exact always; the products may have wrapped).
+ * KDB_ERR_NOMEM: the scratch does not fit.  kernel_ms_out (may be NULL): device time of the sweep, by HIP events.
+ * KDB_GRAM_BLOCK / KDB_GRAM_WG_BINS: the kernel's constants -- vectors per register block, bins one workgroup covers per grid stride.
+ */
+#define KDB_GRAM_MAX 64
+#define KDB_GRAM_BLOCK 4
+#define KDB_GRAM_WG_BINS 512
+int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
+             uint64_t *sums_out   /* 2*n   words: lo, hi of S[i]            */,
+             uint64_t *gram_out   /* 2*n*n words: lo, hi of G[i][j], both triangles filled */,
+             double   *kernel_ms_out /* may be NULL: device time by HIP events */);
+
+/*
  * `counts = counts + counts_` over the files of a samplesheet (kmerdb/__init__.py:1888-1891) without leaving HBM.
  * kdb_fold_file: sync; add the engine's vector (one file's counts) to a second, engine-owned 4^k accumulator;
  * report that file's total_kmers / unique_kmers (its per-file metadata, parse.py:141-147); clear the file vector

@@ -22,6 +22,7 @@
 #include "kdb_scatter_host.hip.h"
 #include "kdb_smallk.hip.h"
 #include "kdb_probe.hip.h"
+#include "kdb_gram.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
 
@@ -645,6 +646,39 @@ const OptRow *find_option(const char *name)
 }
 }  // namespace
 
+// kdb_gram: the launch of one group of rows, by the sizes of its blocks
+namespace {
+
+struct GramGroup { uint32_t row0, nrows; int na, nb; bool diag; };
+
+void gram_launch(const GramGroup &gr, uint32_t gx, const unsigned long long *const *vecs, const kdbgram::Row *rows, uint32_t nchunks, uint32_t pstride, ulonglong2 *partials,
+                 hipStream_t st)
+{
+    const dim3 grid(gx, gr.nrows), block(kdbgram::TPB);
+    const kdbgram::Row *r = rows + gr.row0;
+    ulonglong2 *p = partials + (uint64_t)gr.row0 * pstride * kdbgram::NSLOT;
+#define KDB_GRAM_CASE(NA, NB, DIAG) hipLaunchKernelGGL((kdbgram::gram_kernel<NA, NB, DIAG>), grid, block, 0, st, vecs, r, nchunks, pstride, p)
+    if (gr.diag) {
+        switch (gr.na) {
+            case 1: KDB_GRAM_CASE(1, 1, true); break;
+            case 2: KDB_GRAM_CASE(2, 2, true); break;
+            case 3: KDB_GRAM_CASE(3, 3, true); break;
+            default: KDB_GRAM_CASE(4, 4, true); break;
+        }
+    } else {                                           // (off the diagonal the first block is always a full one)
+        switch (gr.nb) {
+            case 1: KDB_GRAM_CASE(4, 1, false); break;
+            case 2: KDB_GRAM_CASE(4, 2, false); break;
+            case 3: KDB_GRAM_CASE(4, 3, false); break;
+            default: KDB_GRAM_CASE(4, 4, false); break;
+        }
+    }
+#undef KDB_GRAM_CASE
+}
+
+}  // namespace
+
+
 extern "C" {
 
 int kdb_abi_version(void) { return KDB_ABI_VERSION; }
@@ -1092,6 +1126,107 @@ int kdb_nullomers(kdb_engine *e, int folded, uint64_t *ids_out, uint64_t cap, ui
     }
     HIP_TRY(hipStreamSynchronize(e->s_copy));
     HIP_TRY(hipStreamSynchronize(e->s_compute));
+    return KDB_OK;
+}
+
+// ---- exact moments of finished vectors (kdb_gram.hip.h): sums and Gram matrix as 128-bit integers ----
+int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins, uint64_t *sums_out, uint64_t *gram_out, double *kernel_ms_out)
+{
+    constexpr int B = kdbgram::B, NSLOT = kdbgram::NSLOT;
+    if (n < 1 || n > KDB_GRAM_MAX) return fail(KDB_ERR_ARG, "kdb_gram: n=%d, 1..%d vectors supported", n, KDB_GRAM_MAX);
+    if (nbins == 0 || nbins > (1ull << 36)) return fail(KDB_ERR_ARG, "kdb_gram: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)");
+    if (!d_vectors || !sums_out || !gram_out) return fail(KDB_ERR_ARG, "kdb_gram: d_vectors, sums_out and gram_out must not be NULL");
+    for (int i = 0; i < n; i++) {
+        if (!d_vectors[i]) return fail(KDB_ERR_ARG, "kdb_gram: vector %d is NULL", i);
+        if (((uintptr_t)d_vectors[i] & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_gram: vector %d is not 16-byte aligned", i);
+    }
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    DeviceGuard g(device_id);
+
+    // rows = pairs of blocks (bi <= bj), grouped by the kernel that serves them: the last block may hold fewer than B vectors
+    const int nblk = (n + B - 1) / B, last = n - (nblk - 1) * B, nfull = last == B ? nblk : nblk - 1;
+    std::vector<kdbgram::Row> rows;
+    std::vector<GramGroup> groups;
+    auto open_group = [&](int na, int nb, bool diag) { groups.push_back(GramGroup{(uint32_t)rows.size(), 0, na, nb, diag}); };
+    auto close_group = [&]() { groups.back().nrows = (uint32_t)rows.size() - groups.back().row0; if (!groups.back().nrows) groups.pop_back(); };
+    open_group(B, B, true);
+    for (int b = 0; b < nfull; b++) rows.push_back(kdbgram::Row{(uint8_t)b, (uint8_t)b});
+    close_group();
+    open_group(B, B, false);
+    for (int bi = 0; bi < nfull; bi++) for (int bj = bi + 1; bj < nfull; bj++) rows.push_back(kdbgram::Row{(uint8_t)bi, (uint8_t)bj});
+    close_group();
+    if (nfull < nblk) {
+        open_group(last, last, true);
+        rows.push_back(kdbgram::Row{(uint8_t)nfull, (uint8_t)nfull});
+        close_group();
+        open_group(B, last, false);
+        for (int bi = 0; bi < nfull; bi++) rows.push_back(kdbgram::Row{(uint8_t)bi, (uint8_t)nfull});
+        close_group();
+    }
+    const uint32_t nrows = (uint32_t)rows.size();
+    // gram_kernel takes the whole chunks, gram_tail_kernel the bins behind them; a row's partials: one per workgroup, then the tail's
+    const uint32_t nchunks = (uint32_t)(nbins / kdbgram::CHUNK_BINS), wg_chunks = kdbgram::TPB / 64;
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, nrows <= 3 ? 1024u : 256u));       // (any grid gives the same integers)
+    const uint32_t nparts = gx + 1;
+    struct Scratch {
+        const unsigned long long **vecs = nullptr; kdbgram::Row *rows = nullptr; ulonglong2 *partials = nullptr, *out = nullptr;
+        hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
+        ~Scratch()
+        {
+            (void)hipFree(vecs); (void)hipFree(rows); (void)hipFree(partials); (void)hipFree(out);
+            if (a) (void)hipEventDestroy(a);
+            if (b) (void)hipEventDestroy(b);
+            if (st) (void)hipStreamDestroy(st);
+        }
+    } sc;
+    std::vector<const unsigned long long *> ptrs((size_t)nblk * B, (const unsigned long long *)d_vectors[0]);
+    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
+    if (hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess || hipMalloc((void **)&sc.rows, nrows * sizeof(kdbgram::Row)) != hipSuccess ||
+        hipMalloc((void **)&sc.partials, (uint64_t)nrows * nparts * NSLOT * sizeof(ulonglong2)) != hipSuccess ||
+        hipMalloc((void **)&sc.out, (uint64_t)nrows * NSLOT * sizeof(ulonglong2)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_gram: no room for the partial sums of %u x %u workgroups", nrows, gx);
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&sc.a));
+    HIP_TRY(hipEventCreate(&sc.b));
+    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.rows, rows.data(), nrows * sizeof(kdbgram::Row), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    for (const GramGroup &gr : groups) gram_launch(gr, gx, sc.vecs, sc.rows, nchunks, nparts, sc.partials, sc.st);
+    hipLaunchKernelGGL(kdbgram::gram_tail_kernel, dim3(nrows), dim3(64), 0, sc.st, sc.vecs, (const kdbgram::Row *)sc.rows, n, (uint64_t)nchunks * kdbgram::CHUNK_BINS, nbins,
+                       nparts, gx, sc.partials);
+    hipLaunchKernelGGL(kdbgram::gram_combine_kernel, dim3(nrows), dim3(256), 0, sc.st, (const ulonglong2 *)sc.partials, nparts, sc.out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    std::vector<ulonglong2> res((size_t)nrows * NSLOT);
+    HIP_TRY(hipMemcpyAsync(res.data(), sc.out, res.size() * sizeof(ulonglong2), hipMemcpyDeviceToHost, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    if (kernel_ms_out) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
+        *kernel_ms_out = (double)ms;
+    }
+    for (uint32_t r = 0; r < nrows; r++) {
+        const ulonglong2 *slot = &res[(size_t)r * NSLOT];
+        for (int i = 0; i < B; i++) {
+            const int vi = rows[r].bi * B + i;
+            if (vi >= n) continue;
+            if (rows[r].bi == rows[r].bj) { sums_out[2 * vi] = slot[B * B + i].x; sums_out[2 * vi + 1] = slot[B * B + i].y; }
+            for (int j = 0; j < B; j++) {
+                const int vj = rows[r].bj * B + j;
+                if (vj >= n || vj < vi) continue;
+                const ulonglong2 v = slot[i * B + j];
+                gram_out[2 * ((size_t)vi * n + vj)] = gram_out[2 * ((size_t)vj * n + vi)] = v.x;
+                gram_out[2 * ((size_t)vi * n + vj) + 1] = gram_out[2 * ((size_t)vj * n + vi) + 1] = v.y;
+            }
+        }
+    }
+    for (int i = 0; i < n; i++)
+        if (sums_out[2 * i + 1] != 0)
+            return fail(KDB_ERR_ARG, "kdb_gram: the sum of vector %d is 2^64 or more: its products may have wrapped 128 bits", i);
     return KDB_OK;
 }
 

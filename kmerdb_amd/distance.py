@@ -1,0 +1,241 @@
+"""kmerdb_amd.distance -- `kmerdb distance` on count profiles (reference kmerdb/__init__.py:577-813, distance.pyx:108-152).
+
+Every metric the reference offers on count profiles is a function of the vectors' sums S[i], their Gram matrix
+G[i][j] = Sum_b x_i[b] x_j[b] and the number of bins N.  The device computes those as exact 128-bit integers in one sweep of the
+vectors where they lie in HBM (kdb_gram, csrc/kdb_gram.hip.h); the host does the last step in exact integer / 150-digit decimal
+arithmetic, so every value is the float64 nearest the true one, or its neighbour.  No CPU fallback: without a device moments() raises.
+
+Departure from the reference, on purpose: its custom `pearson` (distance.pyx:118-119) rounds both means to float32 before it forms the
+residuals; here the means never exist -- num = N Gxy - Sx Sy is an integer.  `correlation` is scipy's 1 - r, the reference CLI's default.
+"""
+import ctypes
+import decimal
+import os
+import sys
+
+import numpy as np
+
+from . import _abi
+
+METRICS = ("pearson", "correlation", "cosine", "sqeuclidean", "euclidean")
+IDENTITY = {"pearson": 1.0, "correlation": 0.0, "cosine": 0.0, "sqeuclidean": 0.0, "euclidean": 0.0}     # python_distances.identity
+_CTX = decimal.Context(prec=150, Emax=decimal.MAX_EMAX, Emin=decimal.MIN_EMIN)       # vx * vy < 2^330 ~ 1e99: held exactly; the quotient to 150 digits
+
+
+def _require_device(device):
+    n = _abi_device_count()
+    if n < 1 or not 0 <= int(device) < n:
+        raise _abi.KdbHipError("kmerdb_amd.distance needs HIP device {0}; {1} visible (there is no CPU fallback)".format(device, n))
+
+
+def _abi_device_count():
+    n = ctypes.c_int(0)
+    rc = _abi.lib().kdb_device_count(ctypes.byref(n))
+    if rc != _abi.KDB_OK:
+        raise _abi.KdbHipError("no HIP device: {0}".format(_abi.last_error()))
+    return n.value
+
+
+def gram(pointers, nbins, device=0):
+    """kdb_gram on raw device pointers -> (sums, gram, kernel_ms): Python ints, both triangles of gram filled."""
+    n = len(pointers)
+    arr = (ctypes.c_void_p * max(n, 1))(*[ctypes.c_void_p(int(p)) for p in pointers])
+    sums = (ctypes.c_uint64 * (2 * max(n, 1)))()
+    g = (ctypes.c_uint64 * (2 * max(n, 1) * max(n, 1)))()
+    ms = ctypes.c_double(0)
+    _abi.check(_abi.lib().kdb_gram(int(device), arr, n, int(nbins), sums, g, ctypes.byref(ms)))
+    s = [sums[2 * i] | (sums[2 * i + 1] << 64) for i in range(n)]
+    G = [[g[2 * (i * n + j)] | (g[2 * (i * n + j) + 1] << 64) for j in range(n)] for i in range(n)]
+    return s, G, ms.value
+
+
+def moments(vectors, device=0):
+    """-> (sums: list[int], gram: n x n list of Python ints), exact, computed on the device.
+
+    `vectors`: any mix of Engine objects (synced; their table is used in place, never copied), torch int64/uint64 tensors on that
+    device, and host uint64 numpy arrays (uploaded for the call, freed after it).  ValueError if the lengths differ; KdbHipError
+    without a device."""
+    from .engine import Engine
+    _require_device(device)
+    vectors = list(vectors)
+    if not vectors:
+        raise ValueError("moments needs at least one vector")
+    keep, ptrs, lengths = [], [], []
+    torch = None
+    for v in vectors:
+        if isinstance(v, Engine):
+            if v.device != int(device):
+                raise ValueError("an engine on device {0} was given, device {1} asked".format(v.device, device))
+            v.sync()
+            p, nb = v.table_ptr()
+        elif isinstance(v, np.ndarray):
+            if v.dtype != np.uint64 or v.ndim != 1:
+                raise ValueError("host vectors must be one-dimensional uint64 arrays")
+            import torch
+            t = torch.from_numpy(np.ascontiguousarray(v).view(np.int64)).to("cuda:{0}".format(int(device)))
+            keep.append(t)
+            p, nb = t.data_ptr(), t.numel()
+        else:
+            import torch
+            if not isinstance(v, torch.Tensor):
+                raise TypeError("vectors are Engine objects, torch tensors or numpy arrays, not {0}".format(type(v).__name__))
+            if v.dtype not in (torch.int64, torch.uint64) or v.dim() != 1 or not v.is_contiguous():
+                raise ValueError("device vectors must be contiguous one-dimensional int64/uint64 tensors")
+            if v.device.type != "cuda" or v.device.index != int(device):
+                raise ValueError("a tensor on {0} was given, device {1} asked".format(v.device, device))
+            keep.append(v)
+            p, nb = v.data_ptr(), v.numel()
+        ptrs.append(p)
+        lengths.append(int(nb))
+    if len(set(lengths)) != 1:
+        raise ValueError("the vectors differ in length: {0}".format(sorted(set(lengths))))
+    if torch is not None:
+        torch.cuda.synchronize(int(device))              # (uploads and whatever produced the tensors: kdb_gram runs on a stream of its own)
+    s, G, _ = gram(ptrs, lengths[0], device)
+    del keep
+    return s, G
+
+
+def _ratio(num, den2):
+    """num / sqrt(den2) of two integers to 150 digits; None where den2 == 0"""
+    if den2 == 0:
+        return None
+    return _CTX.divide(decimal.Decimal(num), _CTX.sqrt(decimal.Decimal(den2)))
+
+
+def from_moments(sums, gram, nbins, metric):
+    """The n x n float64 matrix of `metric` from exact integer moments (pure host code).
+
+        num = N Gxy - Sx Sy,  vx = N Gxx - Sx^2,  vy likewise
+        pearson      r = num / sqrt(vx vy)          (the reference's custom metric, without its float32 means: distance.pyx:118-119)
+        correlation  1 - r                          (scipy's definition, the reference CLI's default)
+        cosine       1 - Gxy / sqrt(Gxx Gyy)
+        sqeuclidean  Gxx + Gyy - 2 Gxy;   euclidean  its square root
+
+    The diagonal is the metric's identity (1.0 for pearson, 0.0 otherwise, as python_distances.identity); a zero denominator -- a constant
+    vector, or an all-zero one for cosine -- gives nan.  The last step runs in integers and 150-digit decimals: each value is the float64
+    nearest the true one, or its neighbour."""
+    if metric not in METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+    n = len(sums)
+    N = int(nbins)
+    out = np.empty((n, n), dtype=np.float64)
+    one = decimal.Decimal(1)
+    for i in range(n):
+        out[i][i] = IDENTITY[metric]
+        for j in range(i + 1, n):
+            gxx, gyy, gxy = int(gram[i][i]), int(gram[j][j]), int(gram[i][j])
+            if metric in ("pearson", "correlation"):
+                sx, sy = int(sums[i]), int(sums[j])
+                r = _ratio(N * gxy - sx * sy, (N * gxx - sx * sx) * (N * gyy - sy * sy))
+                v = float("nan") if r is None else float(r if metric == "pearson" else _CTX.subtract(one, r))
+            elif metric == "cosine":
+                r = _ratio(gxy, gxx * gyy)
+                v = float("nan") if r is None else float(_CTX.subtract(one, r))
+            else:
+                d2 = gxx + gyy - 2 * gxy
+                v = float(d2) if metric == "sqeuclidean" else float(_CTX.sqrt(decimal.Decimal(d2)))
+            out[i][j] = out[j][i] = v
+    return out
+
+
+def distance_matrix(vectors, metric="correlation", device=0):
+    """moments() on the device, then from_moments()."""
+    if metric not in METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+    vectors = list(vectors)
+    s, G = moments(vectors, device=device)
+    v0 = vectors[0]
+    nbins = v0.nbins if hasattr(v0, "nbins") else (v0.size if isinstance(v0, np.ndarray) else v0.numel())
+    return from_moments(s, G, nbins, metric)
+
+
+def correlation(a, b, total_kmers):
+    """The reference's distance.correlation(a, b, total_kmers) (distance.pyx:108-152), drop-in: Pearson's r of two count vectors of
+    `total_kmers` entries -- exact moments on the device instead of the long double loop with float32 means."""
+    if total_kmers != len(a) or total_kmers != len(b):
+        raise ValueError("NumPy kmer count array total does not match length of arrays")
+    vecs = [np.ascontiguousarray(v, dtype=np.uint64) for v in (a, b)]
+    s, G = moments(vecs)
+    return float(from_moments(s, G, total_kmers, "pearson")[0][1])
+
+
+def format_matrix(dist, columns, output_delimiter="\t"):
+    """What the reference prints (kmerdb/__init__.py:800-813): the one off-diagonal number of a 2 x 2 result; otherwise a header row and rows
+    of repr(float), nan as an empty field -- pandas' DataFrame(dist, columns=columns).to_csv(sep=..., index=False)."""
+    dist = np.asarray(dist, dtype=np.float64)
+    if dist.shape == (2, 2):
+        return "{0}\n".format(repr(float(dist[0][1])))
+    if len(columns) != dist.shape[1]:
+        raise ValueError("{0} column names for {1} columns".format(len(columns), dist.shape[1]))
+    lines = [output_delimiter.join(str(c) for c in columns)]
+    for row in dist:
+        lines.append(output_delimiter.join("" if x != x else repr(float(x)) for x in row))
+    return "\n".join(lines) + "\n"
+
+
+def column_names_for(inputs, column_names=None):
+    """basename.split(".")[0] of every input, or the lines of the names file (kmerdb/__init__.py:645-651)."""
+    if column_names is None:
+        columns = [os.path.basename(p).split(".")[0] for p in inputs]
+    else:
+        with open(column_names) as f:
+            columns = [line.rstrip() for line in f]
+    if len(columns) != len(inputs):
+        raise RuntimeError("Number of column names {0} does not match number of input files {1}...".format(len(columns), len(inputs)))
+    return columns
+
+
+def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None, device=0):
+    """The reference driver for two or more .kdb files (kmerdb/__init__.py:616-661, :796-813): read the profiles, one sweep on the device,
+    print the matrix.  -> the matrix."""
+    from . import fileutil
+    inputs = list(inputs)
+    if metric not in METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+    if len(inputs) < 2:
+        raise ValueError("'kmerdb distance' requires more than one .kdb file as positional inputs")
+    if not all(os.path.splitext(p)[-1] == ".kdb" for p in inputs):
+        raise IOError("One or more parseable .kdb filepaths did not end in '.kdb'")
+    ks = [int(fileutil._read_header(p)["k"]) for p in inputs]
+    if any(k != ks[0] for k in ks):
+        raise TypeError("One or more files did not have k set to be equal to {0}: {1}".format(ks[0], ks))
+    columns = column_names_for(inputs, column_names)
+    _require_device(device)
+    profiles = [fileutil.read_kdb(p).counts for p in inputs]
+    dist = distance_matrix(profiles, metric=metric, device=device)
+    (sys.stdout if out is None else out).write(format_matrix(dist, columns, output_delimiter))
+    return dist
+
+
+def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not_canonicalize=False, device=0):
+    """Count the files of a samplesheet and compare their profiles without leaving HBM: one engine counts each file, its vector is copied
+    device-to-device into row i of one n x 4^k tensor, the engine is reset; then one moments() call.  MemoryError before counting if
+    n * 8 * 4^k plus one engine does not fit the free device memory.  -> (matrix, columns, per-file metadata)."""
+    from . import parse
+    from .engine import Engine, KDB_N_DROP, KDB_N_EXPAND
+    if type(k) is not int:
+        raise TypeError("k must be an int")
+    if metric not in METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+    files = list(files)
+    if not files:
+        raise ValueError("profile_distances needs at least one file")
+    _require_device(device)
+    import torch
+    n, N = len(files), 4 ** k
+    engine_bytes = 8 * N + ((6 << 30) if k >= 13 else (1 << 30))             # the vector and the engine's staging and scatter scratch
+    free_b, _ = torch.cuda.mem_get_info(int(device))
+    if n * 8 * N + engine_bytes > free_b:
+        raise MemoryError("{0} profiles of 4^{1} bins and one engine need {2} bytes of device memory, {3} are free".format(
+            n, k, n * 8 * N + engine_bytes, free_b))
+    rows = torch.empty((n, N), dtype=torch.int64, device="cuda:{0}".format(int(device)))
+    metadata = []
+    with Engine(k, canonicalize=not do_not_canonicalize, n_mode=KDB_N_DROP if no_ambiguous else KDB_N_EXPAND, device=device) as eng:
+        for i, f in enumerate(files):
+            metadata.append(parse.parsefile_folded(f, k, eng, replace_with_none=bool(no_ambiguous), fold=False))
+            rows[i].copy_(eng.table_tensor())
+            torch.cuda.synchronize(int(device))
+            eng.reset()
+    s, G = moments([rows[i] for i in range(n)], device=device)
+    return from_moments(s, G, N, metric), column_names_for(files), metadata

@@ -186,7 +186,8 @@ def profile(inputs, k, output_name, no_ambiguous=False, do_not_canonicalize=Fals
 
 
 def main(argv=None):
-    """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107)."""
+    """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
+    `graph` and `distance <metric> a.kdb b.kdb ...` beside it."""
     import argparse
     ap = argparse.ArgumentParser(prog="kmerdb_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -208,7 +209,17 @@ def main(argv=None):
     gp.add_argument("--device", type=int, default=0)
     gp.add_argument("input", nargs="+")
     gp.add_argument("kdbg")
+    dp = sub.add_parser("distance", help="distance matrix of two or more .kdb count profiles (__init__.py:577-813)")
+    dp.add_argument("metric", choices=["pearson", "correlation", "cosine", "sqeuclidean", "euclidean"])
+    dp.add_argument("--column-names", default=None, help="a file with one column name per line (default: the inputs' basenames)")
+    dp.add_argument("--output-delimiter", default="\t")
+    dp.add_argument("--device", type=int, default=0)
+    dp.add_argument("input", nargs="+")
     a = ap.parse_args(argv)
+    if a.cmd == "distance":
+        from . import distance
+        distance.distances(a.input, a.metric, column_names=a.column_names, output_delimiter=a.output_delimiter, device=a.device)
+        return 0
     if a.cmd == "graph":
         from . import graph
         _, n = graph.make_graph(a.input, a.k, a.kdbg, quiet=a.quiet, do_not_canonicalize=a.do_not_canonicalize,
