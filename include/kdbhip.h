@@ -163,6 +163,17 @@ int kdb_nullomers(kdb_engine *e, int folded, uint64_t *ids_out, uint64_t cap, ui
 int kdb_reduce(kdb_engine *const *engines, int n, int root);
 
 /*
+ * The two strands of a profile, merged (csrc/kdb_strands.hip.h).  d_fwd holds 4^k forward counts, d_table 4^k counts; rc(i) reverses the k
+ * two-bit digits of i and complements each.
+ *   d_table[i] += d_fwd[i] + d_fwd[rc(i)]   for i <  rc(i)
+ *   d_table[i] += d_fwd[i]                  for i == rc(i)
+ *   d_fwd is all zero afterwards; bins of d_table with i > rc(i) are not touched.
+ * A canonical engine does this itself at every kdb_sync (option "strand_merge"); the entry point runs the same kernels on any two
+ * vectors of the caller's.  Both on device_id, 8-byte aligned, not the same vector; k = 1..17.  Returns after the kernel has finished.
+ */
+int kdb_strand_merge(int device_id, void *d_fwd, void *d_table, int k);
+
+/*
  * Exact integer moments of n finished count vectors on one device, in one sweep (csrc/kdb_gram.hip.h): what every distance of
  * `kmerdb distance` on count profiles is a function of (kmerdb/__init__.py:577-813, distance.pyx:108-152; kmerdb_amd/distance.py).
  *   S[i]    = Sum_b x_i[b]            -> sums_out[2 i], [2 i + 1] = low, high 64 bits
@@ -349,7 +360,8 @@ int kdb_read_kdb_rows(const char *path, uint64_t nbins, uint64_t *kmer_ids_out, 
 #define KDB_KERNEL_PAGE_SORT     4   /* pages_count / pages_scan / pages_place (+ l2_plan): page tags -> one page list per bucket */
 #define KDB_KERNEL_PAGE_HIST     5   /* page_hist_kernel: one 32768-bin LDS histogram per bucket, added to the vector */
 #define KDB_KERNEL_STATS         6   /* stats_kernel / fold_kernel: count_nonzero, Sum, samplesheet accumulation */
-#define KDB_N_KERNELS            7
+#define KDB_KERNEL_STRAND_MERGE   7   /* strand_merge_kernel: forward counts of a canonical engine -> canonical bins of the vector, once per sync */
+#define KDB_N_KERNELS            8
 int         kdb_prof_enable(kdb_engine *e, int on);
 int         kdb_prof_reset(kdb_engine *e);
 int         kdb_prof_get(kdb_engine *e, int kernel_id, double *total_ms, uint64_t *launches);
@@ -380,6 +392,13 @@ const char *kdb_prof_kernel_name(int kernel_id);
  *        workgroups of 512 -- the form of rounds 2-4, kept for comparison: the memory system takes random 64-byte writes at 3.4-4.6 TB/s
  *        and 128-byte ones at 5.3);  "l1_compiled_k" 1/0 (k = 15: level 1 / level 2 with their shifts compiled in);
  *        "l1_one_round" 1/0 (default 1: level 1 of k <= 15 with 128 rings of 256 elements -- one placement round per tile -- instead of 256 of 128).
+ *        "strand_merge" 1/0 (default 1: a canonical engine's batches of the one-level paths -- k <= 8 in LDS, k = 9..12 through one scatter
+ *        level -- count FORWARD ids into a staging vector of the engine's own, 4^k uint64 allocated at the first such batch, and kdb_sync adds
+ *        both strands to the count vector at the canonical bins, kdb_strand_merge; 0: min(forward, reverse complement) per window in the
+ *        counting kernels.  The vector a caller reads after a sync is the same either way; it is not written between syncs when the option
+ *        is on.  Not used with "overlap" or "smallk_old", nor when the staging vector cannot be allocated),  "strand_merge_max_k" (1..17,
+ *        default 12: the largest k that is staged; 13 stages k = 13's one-level path too -- 512 MiB, measured no faster --, and the two-level
+ *        paths, k > "one_level_max_k", never are).  Setting either syncs first.
  *        The environment variable KDB_ENGINE_OPTS="name=value,..." sets options for every engine a process creates (experiments, the test
  *        suite under an option); an unknown name fails kdb_create.
  *   get: "sc_wide_lines", "l1_wide_lines", "l2_wide_lines", "l1_one_round", "reserve_bytes", "arena_budget_bytes" (what the arena may grow to, once decided), "free_at_sizing" (free device memory when it
@@ -389,7 +408,7 @@ const char *kdb_prof_kernel_name(int kernel_id);
  *        (bytes of count vector copied to the host so far), "folded_files", "sc_lo_bits", "sc_contig_pages", "arena_grow",
  *        "arena_batches", "arena_pages" / "arena_reallocs" (size of the page arena in 1 KiB pages; times it was (re)allocated),
  *        "arena_cursor" / "arena_used_bound" / "arena_worst_case" (pages the pending batches hold: on the device, by the host's
- *        present bound, and by their worst cases added up), "one_level_max_k", "smallk_old",
+ *        present bound, and by their worst cases added up), "one_level_max_k", "smallk_old", "strand_merge", "strand_merge_max_k",
  *        "hist_flushes" / "flushed_batches" / "full_flushes" (k >= 13: histogram passes over the arena, the batches they added
  *        to the vector, and how many of the passes a full arena forced), "bytes_in" and the
  *        device counters "pages_bases", "lines_bases", "pages_ids", "lines_ids", "table_bytes", "total_kmers" (what the

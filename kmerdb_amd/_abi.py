@@ -16,7 +16,7 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 KDB_OK, KDB_ERR_ARG, KDB_ERR_HIP, KDB_ERR_SHORT_READ, KDB_ERR_BAD_RESIDUE, KDB_ERR_NOMEM, KDB_ERR_STATE = range(7)
 KDB_N_DROP, KDB_N_EXPAND = 0, 1
 KDB_SUBMIT_PINNED, KDB_SUBMIT_CONTINUES = 1, 2
-KDB_N_KERNELS = 7
+KDB_N_KERNELS = 8
 KDB_GRAM_MAX, KDB_GRAM_BLOCK, KDB_GRAM_WG_BINS = 64, 4, 512
 ABI_VERSION = 6
 
@@ -45,6 +45,7 @@ SYMBOLS = (
     ("kdb_reduce", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
     ("kdb_gram", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_uint64, _u64p, _u64p,
                                 ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_strand_merge", ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int]),
     ("kdb_fold_file", ctypes.c_int, [_vp, _u64p, _u64p]),
     ("kdb_fold_file_into", ctypes.c_int, [_vp, _vp, _u64p, _u64p]),
     ("kdb_finish_folded", ctypes.c_int, [_vp, _vp, _u64p, _u64p]),

@@ -23,6 +23,7 @@
 #include "kdb_smallk.hip.h"
 #include "kdb_probe.hip.h"
 #include "kdb_gram.hip.h"
+#include "kdb_strands.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
 
@@ -51,7 +52,7 @@ int fail(int code, const char *fmt, ...)
 
 constexpr int NBUF = 2;                                  // double-buffered staging
 const char *const KERNEL_NAMES[KDB_N_KERNELS] = {
-    "lens+mark_reads_kernel", "count_kernel", "scatter_bases_kernel", "scatter_ids_kernel", "pages_sort_kernels", "page_hist_kernel", "stats_kernel"};
+    "lens+mark_reads_kernel", "count_kernel", "scatter_bases_kernel", "scatter_ids_kernel", "pages_sort_kernels", "page_hist_kernel", "stats_kernel", "strand_merge_kernel"};
 
 struct ProfSpan { hipEvent_t a, b; int kernel; };
 
@@ -152,6 +153,12 @@ struct kdb_engine {
     kdb::OverlapState ov;
     kdb::TwoLevelPaged tp;            // its two-level form (k = 13..17): level-1 scratch and the arena of pending level-2 pages
     int64_t oom_fallbacks = 0;        // batches that fell back to direct atomics because scratch did not fit
+    // canonical engines, one-level LDS-histogram paths: batches count forward ids into d_fwd, kdb_sync adds both strands to d_table
+    // at the canonical bins (kdb_strands.hip.h).  d_table itself is only ever added to, at canonical bins, as without the staging.
+    int strand_merge = 1;             // 0: min(fwd, rc) per window in the counting kernels, straight into d_table
+    int strand_merge_max_k = 12;      // the largest k that is staged (never more than one_level_max_k); k = 13 measured no faster, DESIGN.md section 4
+    unsigned long long *d_fwd = nullptr;             // 4^k uint64, allocated at the first staged batch; all zero unless strands_pending
+    bool strands_pending = false;
 
     // ids-only engines (kdb_create_ids) have no count vector; scratch of kdb_shred / kdb_window_ids (grow-only)
     bool tableless = false;
@@ -339,6 +346,29 @@ int flush_accumulated(kdb_engine *e)
     return KDB_OK;
 }
 
+// the staging vector of forward counts, allocated and zeroed at its first use.  No room for it: the batch in hand is counted canonically
+// into d_table as without it (not an oom_fallback: no scratch was refused), and the next batch asks again.
+bool ensure_fwd(kdb_engine *e)
+{
+    if (e->d_fwd) return true;
+    if (hipMalloc((void **)&e->d_fwd, e->nbins * 8ull) != hipSuccess) { (void)hipGetLastError(); e->d_fwd = nullptr; return false; }
+    if (hipMemsetAsync(e->d_fwd, 0, e->nbins * 8ull, e->s_compute) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(e->d_fwd); e->d_fwd = nullptr; return false; }
+    return true;
+}
+
+// add the staged forward counts to the vector at the canonical bins and clear them; on s_compute, after everything that wrote d_fwd
+int merge_strands(kdb_engine *e)
+{
+    if (!e->strands_pending) return KDB_OK;
+    {
+        ProfScope ps(e, KDB_KERNEL_STRAND_MERGE);
+        kdbstrands::strand_merge_launch(e->s_compute, e->d_fwd, e->d_table, e->k);
+    }
+    e->strands_pending = false;
+    HIP_TRY(hipGetLastError());
+    return KDB_OK;
+}
+
 // launch the counting kernels over one device-resident batch, on s_compute
 int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t *d_offs, size_t nreads, int first_is_continuation, int flags)
 {
@@ -404,16 +434,22 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
     const bool paged2 = algo == 2 && e->k > e->opt.one_level_max_k;
     // only the deferred two-level flush may treat the vector as still all zero; everything else adds to it right away
     if (!paged2 || e->n_mode == KDB_N_EXPAND || !e->opt.defer) e->tp.table_is_zero = false;
+    // a canonical batch of the one-level paths counts forward ids into the staging vector; the strands are merged at the sync
+    const bool staged = e->canonical && e->strand_merge && algo == 2 && e->k <= std::min((int)e->opt.one_level_max_k, e->strand_merge_max_k) &&
+                        !e->overlap && !e->smallk_old && ensure_fwd(e);
+    const int canonical = staged ? 0 : e->canonical;
+    unsigned long long *const table = staged ? e->d_fwd : e->d_table;
+    if (staged) e->strands_pending = true;
     if (algo == 2) {
         EngineProf hook(e);
         const bool ex = e->n_mode == KDB_N_EXPAND;
-        const kdb::ScBatch batch{d_bases, nbytes, rs, e->k, e->canonical, ex, e->d_table, e->d_ctr};
+        const kdb::ScBatch batch{d_bases, nbytes, rs, e->k, canonical, ex, table, e->d_ctr};
         int rc;
         if (e->k <= kdb::SMALLK_LDS_MAX_K && !e->smallk_old)
-            rc = kdb::smallk_lds_count(e->s_compute, d_bases, nbytes, rs, e->k, e->canonical, ex, e->opt.grid, e->d_table, e->d_ctr, hook);
+            rc = kdb::smallk_lds_count(e->s_compute, d_bases, nbytes, rs, e->k, canonical, ex, e->opt.grid, table, e->d_ctr, hook);
         else if (e->k <= kdb::SMALLK_MAX) {
             mark();
-            rc = kdb::smallk_count(e->s_compute, d_bases, nbytes, e->k, e->canonical, ex, e->d_table, e->d_ctr, hook);
+            rc = kdb::smallk_count(e->s_compute, d_bases, nbytes, e->k, canonical, ex, table, e->d_ctr, hook);
             unmark();
         }
         else if (e->k <= e->opt.one_level_max_k) {
@@ -440,7 +476,7 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
             const dim3 grid((unsigned)ntiles), block(kdb::TPB);
 #define KDB_LAUNCH_DIRECT(ID, EX)                                                                              \
     hipLaunchKernelGGL((kdb::count_direct_kernel<ID, EX>), grid, block, 0, e->s_compute, d_bases, (uint64_t)nbytes, \
-                       e->k, e->canonical, e->d_table, e->d_ctr)
+                       e->k, canonical, table, e->d_ctr)
             if (e->k <= 16) { if (ex) KDB_LAUNCH_DIRECT(uint32_t, true); else KDB_LAUNCH_DIRECT(uint32_t, false); }
             else            { if (ex) KDB_LAUNCH_DIRECT(uint64_t, true); else KDB_LAUNCH_DIRECT(uint64_t, false); }
 #undef KDB_LAUNCH_DIRECT
@@ -449,7 +485,7 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
     }
     if (e->n_mode == KDB_N_EXPAND && e->d_worklist) {
         ProfScope ps(e, KDB_KERNEL_COUNT);
-        hipLaunchKernelGGL(kdb::expand_worklist_kernel, dim3(1024), dim3(256), 0, e->s_compute, e->d_table, e->d_ctr, e->k, e->canonical);
+        hipLaunchKernelGGL(kdb::expand_worklist_kernel, dim3(1024), dim3(256), 0, e->s_compute, table, e->d_ctr, e->k, canonical);
     }
     if (e->n_mode == KDB_N_DROP) {
         // residues that are neither ACGT nor N: an IUPAC code is only an error in a window that no N shields (kmer.py:287-289)
@@ -579,7 +615,7 @@ constexpr int N_PROBES = (int)(sizeof(PROBES) / sizeof(PROBES[0]));
 // ---- the engine's plain integer options (kdb_set_option / kdb_get_option): one row each; the odd ones are code in those two functions ----
 namespace {
 enum OptBefore { OPT_NOTHING, OPT_FLUSH_PENDING /* pending batches were scattered under the old value */, OPT_SYNC_AND_STREAMS /* kdb_sync, then overlap_streams */,
-                 OPT_NO_STAGING /* refused once the staging buffers exist */ };
+                 OPT_SYNC /* kdb_sync: staged strands are merged under the old value */, OPT_NO_STAGING /* refused once the staging buffers exist */ };
 struct OptRow {
     const char *name;
     int64_t (*get)(kdb_engine *);
@@ -603,6 +639,8 @@ const OptRow OPTIONS[] = {
     {"overlap", KDB_OPT(overlap), true, 0, 1024, OPT_SYNC_AND_STREAMS},
     {"overlap_hist_cus", KDB_OPT(overlap_hist_cus), false, 0, 1024, OPT_SYNC_AND_STREAMS},
     {"overlap_mask_mode", KDB_OPT(overlap_mask_mode), false, 0, 1024, OPT_SYNC_AND_STREAMS},
+    {"strand_merge", KDB_OPT(strand_merge), true, 0, 1024, OPT_SYNC},
+    {"strand_merge_max_k", KDB_OPT(strand_merge_max_k), false, 1, 17, OPT_SYNC, " (1..17; never more than one_level_max_k)"},
     // the paged paths' tuning (kdb::PagedOptions)
     {"sc_grid", KDB_OPT(opt.grid), false, 0, 1024, OPT_NOTHING, " (0..1024)"},
     // id = [ hi ][ bucket fields ][ lo ]: how many of a bucket's 15 (k = 17: 16) bin bits sit below the bucket field
@@ -780,6 +818,7 @@ int kdb_destroy(kdb_engine *e)
     if (e->sh_ids) (void)hipFree(e->sh_ids);
     if (e->sh_ctr) (void)hipFree(e->sh_ctr);
     if (e->d_acc_table) (void)hipFree(e->d_acc_table);
+    if (e->d_fwd) (void)hipFree(e->d_fwd);
     if (e->d_ctr) (void)hipFree(e->d_ctr);
     if (e->owns_table && e->d_table) (void)hipFree(e->d_table);
     if (e->s_compute) (void)hipStreamDestroy(e->s_compute);
@@ -799,6 +838,7 @@ int kdb_reset(kdb_engine *e)
     if (e->s_hist) { HIP_TRY(hipStreamSynchronize(e->s_hist)); e->ov.last = -1; }
     if (e->nbins) HIP_TRY(hipMemsetAsync(e->d_table, 0, e->nbins * 8ull, e->s_compute));
     if (e->d_acc_table) HIP_TRY(hipMemsetAsync(e->d_acc_table, 0, e->nbins * 8ull, e->s_compute));
+    if (e->strands_pending) { HIP_TRY(hipMemsetAsync(e->d_fwd, 0, e->nbins * 8ull, e->s_compute)); e->strands_pending = false; }   // (staged counts go with the vector)
     e->folded_files = e->folded_total = 0;
     e->tp.table_is_zero = e->owns_table && !e->table_escaped;             // (a caller-owned vector may be written by the caller at any time)
     HIP_TRY(hipMemsetAsync(e->d_ctr, 0, sizeof(kdb::DevCounters), e->s_compute));
@@ -960,6 +1000,7 @@ int kdb_sync(kdb_engine *e)
     DeviceGuard g(e->device);
     { int rc = flush_accumulated(e); if (rc != KDB_OK) return rc; }
     { int rc = flush_pending_paged(e); if (rc != KDB_OK) return rc; }
+    { int rc = merge_strands(e); if (rc != KDB_OK) return rc; }
     HIP_TRY(hipStreamSynchronize(e->s_copy));
     HIP_TRY(hipStreamSynchronize(e->s_compute));
     if (e->s_hist) { HIP_TRY(hipStreamSynchronize(e->s_hist)); e->ov.last = -1; }
@@ -1227,6 +1268,23 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
     for (int i = 0; i < n; i++)
         if (sums_out[2 * i + 1] != 0)
             return fail(KDB_ERR_ARG, "kdb_gram: the sum of vector %d is 2^64 or more: its products may have wrapped 128 bits", i);
+    return KDB_OK;
+}
+
+int kdb_strand_merge(int device_id, void *d_fwd, void *d_table, int k)
+{
+    if (k < 1 || k > 17) return fail(KDB_ERR_ARG, "kdb_strand_merge: k=%d outside 1..17", k);
+    if (!d_fwd || !d_table || d_fwd == d_table) return fail(KDB_ERR_ARG, "kdb_strand_merge: d_fwd and d_table must be two vectors");
+    if ((((uintptr_t)d_fwd | (uintptr_t)d_table) & 7u) != 0) return fail(KDB_ERR_ARG, "kdb_strand_merge: the vectors must be 8-byte aligned");
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    DeviceGuard g(device_id);
+    struct Stream { hipStream_t st = nullptr; ~Stream() { if (st) (void)hipStreamDestroy(st); } } s;
+    HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+    kdbstrands::strand_merge_launch(s.st, (unsigned long long *)d_fwd, (unsigned long long *)d_table, k);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s.st));
     return KDB_OK;
 }
 
@@ -1734,11 +1792,11 @@ int kdb_set_option(kdb_engine *e, const char *name, int64_t value)
         if (rc != KDB_OK) return rc;
     }
     if (!strcmp(name, "pending_budget")) e->tp.budget_decided = 0;      // (pending_budget = 0: the arena's size is decided anew at its next use)
-    if (row->before != OPT_SYNC_AND_STREAMS) { row->set(e, row->boolean ? (value ? 1 : 0) : value); return KDB_OK; }
+    if (row->before != OPT_SYNC_AND_STREAMS && row->before != OPT_SYNC) { row->set(e, row->boolean ? (value ? 1 : 0) : value); return KDB_OK; }
     DeviceGuard g(e->device);
     { int rc = kdb_sync(e); if (rc != KDB_OK) return rc; }
     row->set(e, row->boolean ? (value ? 1 : 0) : value);
-    return overlap_streams(e);
+    return row->before == OPT_SYNC ? KDB_OK : overlap_streams(e);
 }
 
 int kdb_get_option(kdb_engine *e, const char *name, int64_t *value)
