@@ -194,6 +194,36 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
              double   *kernel_ms_out /* may be NULL: device time by HIP events */);
 
 /*
+ * The abundance spectrum of one finished count vector -- how many bins hold each count value -- in one sweep on the device
+ * (csrc/kdb_spectrum.hip.h): the reference's util.get_histo (kmerdb/util.py:92-116), and what a rank transform starts from.
+ *   dense_out[v]     = number of bins that hold v, for v < KDB_SPECTRUM_DENSE; exact uint64 (at k = 17 the entry of 0 passes 2^32)
+ *   over_values_out  = every value >= KDB_SPECTRUM_DENSE, once per occurrence, in no particular order; *n_over_out of them
+ * d_vector: nbins uint64 on device_id, 16-byte aligned, read only.  Synchronous; the caller has synchronised whatever produced the
+ * vector; scratch is allocated and freed inside the call.  *n_over_out is always set; over_values_out may be NULL to ask for the
+ * table and the number alone, otherwise it holds over_cap entries (KDB_ERR_ARG if fewer than *n_over_out, with *n_over_out and the
+ * table set).  KDB_ERR_ARG: a NULL or misaligned pointer, nbins == 0 or above 2^36.  KDB_ERR_NOMEM: the scratch does not fit.
+ * kernel_ms_out (may be NULL): device time of the sweep, by HIP events.
+ * KDB_SPECTRUM_WG_BINS: bins one workgroup of either kernel covers per grid stride.
+ */
+#define KDB_SPECTRUM_DENSE 65536
+#define KDB_SPECTRUM_WG_BINS 1024
+int kdb_spectrum(int device_id, const void *d_vector, uint64_t nbins,
+                 uint64_t *dense_out       /* KDB_SPECTRUM_DENSE words */,
+                 uint64_t *over_values_out /* may be NULL */, uint64_t over_cap, uint64_t *n_over_out,
+                 double   *kernel_ms_out   /* may be NULL */);
+
+/*
+ * The vector's doubled mid-ranks: d_ranks_out[b] = 2 #{c : x[c] < x[b]} + #{c : x[c] == x[b]} + 1 as uint64 -- twice what
+ * scipy.stats.rankdata gives, an integer; Pearson's r of two such vectors is Spearman's rho of the counts (python_distances.py:95-114).
+ * One spectrum sweep, the rank tables on the host (the list of large values is copied back, sorted and ranked there), one elementwise
+ * sweep.  d_ranks_out: nbins uint64 on the same device, 16-byte aligned; it may be d_vector itself.  Conventions as above.
+ * KDB_ERR_ARG also for nbins >= 2^32, before anything is read: the ranks sum to nbins (nbins + 1), which the moments of the ranks
+ * need below 2^64.  kernel_ms_out (may be NULL): device time of both sweeps.
+ */
+int kdb_rank_transform(int device_id, const void *d_vector, uint64_t nbins, void *d_ranks_out /* may equal d_vector */,
+                       double *kernel_ms_out);
+
+/*
  * `counts = counts + counts_` over the files of a samplesheet (kmerdb/__init__.py:1888-1891) without leaving HBM.
  * kdb_fold_file: sync; add the engine's vector (one file's counts) to a second, engine-owned 4^k accumulator;
  * report that file's total_kmers / unique_kmers (its per-file metadata, parse.py:141-147); clear the file vector

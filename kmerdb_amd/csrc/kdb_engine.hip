@@ -23,6 +23,8 @@
 #include "kdb_smallk.hip.h"
 #include "kdb_probe.hip.h"
 #include "kdb_gram.hip.h"
+#include "kdb_spectrum.hip.h"
+#include "kdb_spectrum_host.cpp.h"
 #include "kdb_strands.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
@@ -1268,6 +1270,152 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
     for (int i = 0; i < n; i++)
         if (sums_out[2 * i + 1] != 0)
             return fail(KDB_ERR_ARG, "kdb_gram: the sum of vector %d is 2^64 or more: its products may have wrapped 128 bits", i);
+    return KDB_OK;
+}
+
+// ---- abundance spectrum and doubled mid-ranks of a finished vector (kdb_spectrum.hip.h, kdb_spectrum_host.cpp.h) ----
+namespace {
+struct SpectrumScratch {
+    unsigned long long *dense = nullptr;       // DENSE words, then the overflow list's counter
+    unsigned long long *over = nullptr;        // `cap` values
+    unsigned long long *tables = nullptr;      // kdb_rank_transform: the dense rank table, the distinct overflow values, their ranks
+    uint64_t cap = 0;
+    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
+    ~SpectrumScratch()
+    {
+        (void)hipFree(dense); (void)hipFree(over); (void)hipFree(tables);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+// what both entry points check first; nothing on the device is touched
+int spectrum_check_args(const char *who, int device_id, const void *d_vector, uint64_t nbins)
+{
+    if (!d_vector) return fail(KDB_ERR_ARG, "%s: the vector is NULL", who);
+    if (((uintptr_t)d_vector & 15u) != 0) return fail(KDB_ERR_ARG, "%s: the vector is not 16-byte aligned", who);
+    if (nbins == 0 || nbins > kdbspectrum::MAX_BINS) return fail(KDB_ERR_ARG, "%s: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)", who);
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    return KDB_OK;
+}
+
+// (re)allocate the list for `cap` values; the table, the stream and the events at the first call
+int spectrum_alloc(const char *who, SpectrumScratch &sc, uint64_t cap)
+{
+    if (!sc.dense && hipMalloc((void **)&sc.dense, (kdbspectrum::DENSE + 1) * 8ull) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "%s: no room for the table of %u multiplicities", who, kdbspectrum::DENSE);
+    }
+    (void)hipFree(sc.over);
+    sc.over = nullptr;
+    sc.cap = 0;
+    if (cap && hipMalloc((void **)&sc.over, cap * 8ull) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "%s: no room for a list of %llu values of 65536 and above", who, (unsigned long long)cap);
+    }
+    sc.cap = cap;
+    if (!sc.st) {
+        HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreate(&sc.a));
+        HIP_TRY(hipEventCreate(&sc.b));
+    }
+    return KDB_OK;
+}
+
+// one sweep: host[0 .. DENSE) = the multiplicities, host[DENSE] = how many values the list would hold (sc.cap of them are stored); *ms += device time
+int spectrum_sweep(SpectrumScratch &sc, const void *d_vector, uint64_t nbins, std::vector<uint64_t> &host, double *ms)
+{
+    const uint64_t nchunks = nbins / kdbspectrum::CHUNK_BINS;
+    host.assign(kdbspectrum::DENSE + 1, 0);
+    HIP_TRY(hipMemsetAsync(sc.dense, 0, (kdbspectrum::DENSE + 1) * 8ull, sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    hipLaunchKernelGGL(kdbspectrum::spectrum_kernel, dim3(kdbspectrum::spectrum_grid(nchunks)), dim3(kdbspectrum::TPB), 0, sc.st,
+                       (const unsigned long long *)d_vector, nbins, nchunks, sc.dense, sc.over, (unsigned long long)sc.cap, sc.dense + kdbspectrum::DENSE);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    HIP_TRY(hipMemcpyAsync(host.data(), sc.dense, (kdbspectrum::DENSE + 1) * 8ull, hipMemcpyDeviceToHost, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    float t = 0;
+    HIP_TRY(hipEventElapsedTime(&t, sc.a, sc.b));
+    *ms += (double)t;
+    uint64_t total = host[kdbspectrum::DENSE];
+    for (uint32_t v = 0; v < kdbspectrum::DENSE; v++) total += host[v];
+    if (total != nbins) return fail(KDB_ERR_HIP, "the spectrum holds %llu bins, the vector %llu", (unsigned long long)total, (unsigned long long)nbins);
+    return KDB_OK;
+}
+}  // namespace
+
+int kdb_spectrum(int device_id, const void *d_vector, uint64_t nbins, uint64_t *dense_out, uint64_t *over_values_out, uint64_t over_cap,
+                 uint64_t *n_over_out, double *kernel_ms_out)
+{
+    if (n_over_out) *n_over_out = 0;
+    if (!dense_out || !n_over_out) return fail(KDB_ERR_ARG, "kdb_spectrum: dense_out and n_over_out must not be NULL");
+    int rc = spectrum_check_args("kdb_spectrum", device_id, d_vector, nbins);
+    if (rc != KDB_OK) return rc;
+    DeviceGuard g(device_id);
+    SpectrumScratch sc;
+    if ((rc = spectrum_alloc("kdb_spectrum", sc, over_values_out ? std::min(over_cap, nbins) : 0)) != KDB_OK) return rc;
+    std::vector<uint64_t> host;
+    double ms = 0;
+    if ((rc = spectrum_sweep(sc, d_vector, nbins, host, &ms)) != KDB_OK) return rc;
+    const uint64_t n_over = host[kdbspectrum::DENSE];
+    memcpy(dense_out, host.data(), kdbspectrum::DENSE * 8ull);
+    *n_over_out = n_over;
+    if (kernel_ms_out) *kernel_ms_out = ms;
+    if (!over_values_out || n_over == 0) return KDB_OK;
+    if (n_over > over_cap) return fail(KDB_ERR_ARG, "kdb_spectrum: %llu values of 65536 and above do not fit the %llu entries given", (unsigned long long)n_over, (unsigned long long)over_cap);
+    HIP_TRY(hipMemcpy(over_values_out, sc.over, n_over * 8ull, hipMemcpyDeviceToHost));
+    return KDB_OK;
+}
+
+int kdb_rank_transform(int device_id, const void *d_vector, uint64_t nbins, void *d_ranks_out, double *kernel_ms_out)
+{
+    if (nbins >= (1ull << 32)) return fail(KDB_ERR_ARG, "kdb_rank_transform: nbins is 2^32 or more (k >= 16): the doubled ranks sum to N (N + 1), which kdb_gram needs below 2^64");
+    if (!d_ranks_out || ((uintptr_t)d_ranks_out & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_rank_transform: the output is NULL or not 16-byte aligned");
+    int rc = spectrum_check_args("kdb_rank_transform", device_id, d_vector, nbins);
+    if (rc != KDB_OK) return rc;
+    DeviceGuard g(device_id);
+    SpectrumScratch sc;
+    std::vector<uint64_t> host;
+    double ms = 0;
+    // the list is short on count profiles (at most Sum counts / 65536 values): a first guess, and a second sweep with the exact length where it was wrong
+    if ((rc = spectrum_alloc("kdb_rank_transform", sc, std::min<uint64_t>(nbins, 1u << 20))) != KDB_OK) return rc;
+    if ((rc = spectrum_sweep(sc, d_vector, nbins, host, &ms)) != KDB_OK) return rc;
+    if (host[kdbspectrum::DENSE] > sc.cap) {
+        if ((rc = spectrum_alloc("kdb_rank_transform", sc, host[kdbspectrum::DENSE])) != KDB_OK) return rc;
+        if ((rc = spectrum_sweep(sc, d_vector, nbins, host, &ms)) != KDB_OK) return rc;
+        if (host[kdbspectrum::DENSE] > sc.cap) return fail(KDB_ERR_STATE, "kdb_rank_transform: the vector changed during the call");
+    }
+    const uint64_t n_over = host[kdbspectrum::DENSE];
+    std::vector<uint64_t> over(n_over);
+    if (n_over) HIP_TRY(hipMemcpy(over.data(), sc.over, n_over * 8ull, hipMemcpyDeviceToHost));
+    kdbspectrum_host::RankTables t;
+    kdbspectrum_host::rank_tables(host.data(), kdbspectrum::DENSE, over.data(), n_over, t);
+    if (t.nbins != nbins) return fail(KDB_ERR_HIP, "kdb_rank_transform: the rank tables cover %llu bins of %llu", (unsigned long long)t.nbins, (unsigned long long)nbins);
+    const uint64_t nd = t.over_values.size();
+    if (hipMalloc((void **)&sc.tables, (kdbspectrum::DENSE + 2 * nd) * 8ull) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_rank_transform: no room for the rank tables of %llu large values", (unsigned long long)nd);
+    }
+    HIP_TRY(hipMemcpyAsync(sc.tables, t.rank_dense.data(), kdbspectrum::DENSE * 8ull, hipMemcpyHostToDevice, sc.st));
+    if (nd) {
+        HIP_TRY(hipMemcpyAsync(sc.tables + kdbspectrum::DENSE, t.over_values.data(), nd * 8ull, hipMemcpyHostToDevice, sc.st));
+        HIP_TRY(hipMemcpyAsync(sc.tables + kdbspectrum::DENSE + nd, t.over_ranks.data(), nd * 8ull, hipMemcpyHostToDevice, sc.st));
+    }
+    const kdbspectrum::RankTables dt{sc.tables, sc.tables + kdbspectrum::DENSE, sc.tables + kdbspectrum::DENSE + nd, (uint32_t)nd};
+    const uint64_t nchunks = nbins / kdbspectrum::CHUNK_BINS;
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    hipLaunchKernelGGL(kdbspectrum::rank_map_kernel, dim3(kdbspectrum::spectrum_grid(nchunks)), dim3(kdbspectrum::TPB), 0, sc.st,
+                       (const unsigned long long *)d_vector, nbins, nchunks, dt, (unsigned long long *)d_ranks_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    float tm = 0;
+    HIP_TRY(hipEventElapsedTime(&tm, sc.a, sc.b));
+    if (kernel_ms_out) *kernel_ms_out = ms + (double)tm;
     return KDB_OK;
 }
 

@@ -7,6 +7,10 @@ arithmetic, so every value is the float64 nearest the true one, or its neighbour
 
 Departure from the reference, on purpose: its custom `pearson` (distance.pyx:118-119) rounds both means to float32 before it forms the
 residuals; here the means never exist -- num = N Gxy - Sx Sy is an integer.  `correlation` is scipy's 1 - r, the reference CLI's default.
+
+`spearman` (python_distances.py:95-114) is not a function of the count moments, but it is one of the moments of the ranks: rho is
+Pearson's r of the mid-ranks.  The device ranks each vector (kdb_rank_transform: doubled mid-ranks, integers; kmerdb_amd/spectrum.py), then
+the same exact path runs on the rank vectors.  k <= 15: the doubled ranks of N bins sum to N (N + 1), which kdb_gram needs below 2^64.
 """
 import ctypes
 import decimal
@@ -18,6 +22,8 @@ import numpy as np
 from . import _abi
 
 METRICS = ("pearson", "correlation", "cosine", "sqeuclidean", "euclidean")
+RANK_METRICS = ("spearman",)                                                         # Pearson's r of the vectors' ranks: the device ranks first
+RANK_MAX_BINS = 1 << 32                                                              # kdb_rank_transform refuses this many bins and more
 IDENTITY = {"pearson": 1.0, "correlation": 0.0, "cosine": 0.0, "sqeuclidean": 0.0, "euclidean": 0.0}     # python_distances.identity
 _CTX = decimal.Context(prec=150, Emax=decimal.MAX_EMAX, Emin=decimal.MIN_EMIN)       # vx * vy < 2^330 ~ 1e99: held exactly; the quotient to 150 digits
 
@@ -49,47 +55,73 @@ def gram(pointers, nbins, device=0):
     return s, G, ms.value
 
 
+def _device_vector(v, device):
+    """One vector as moments() takes them -> (device pointer, number of bins, the tensor that keeps the memory alive or None for an engine).
+    An engine is synced and its table used in place; a host array is uploaded; the caller synchronises the device before a kdb_ call."""
+    from .engine import Engine
+    if isinstance(v, Engine):
+        if v.device != int(device):
+            raise ValueError("an engine on device {0} was given, device {1} asked".format(v.device, device))
+        v.sync()
+        p, nb = v.table_ptr()
+        return p, int(nb), None
+    if isinstance(v, np.ndarray):
+        if v.dtype != np.uint64 or v.ndim != 1:
+            raise ValueError("host vectors must be one-dimensional uint64 arrays")
+        import torch
+        t = torch.from_numpy(np.ascontiguousarray(v).view(np.int64)).to("cuda:{0}".format(int(device)))
+        return t.data_ptr(), int(t.numel()), t
+    import torch
+    if not isinstance(v, torch.Tensor):
+        raise TypeError("vectors are Engine objects, torch tensors or numpy arrays, not {0}".format(type(v).__name__))
+    if v.dtype not in (torch.int64, torch.uint64) or v.dim() != 1 or not v.is_contiguous():
+        raise ValueError("device vectors must be contiguous one-dimensional int64/uint64 tensors")
+    if v.device.type != "cuda" or v.device.index != int(device):
+        raise ValueError("a tensor on {0} was given, device {1} asked".format(v.device, device))
+    return v.data_ptr(), int(v.numel()), v
+
+
+def _length(v):
+    """number of bins of a vector as moments() takes them, without touching the device"""
+    if hasattr(v, "nbins"):
+        return int(v.nbins)
+    if isinstance(v, np.ndarray):
+        return int(v.size)
+    if hasattr(v, "numel"):
+        return int(v.numel())
+    raise TypeError("vectors are Engine objects, torch tensors or numpy arrays, not {0}".format(type(v).__name__))
+
+
+def _check_metric(metric):
+    if metric not in METRICS + RANK_METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS + RANK_METRICS)))
+
+
+def _check_rank_bins(nbins):
+    if nbins >= RANK_MAX_BINS:
+        raise ValueError("spearman serves k <= 15: {0} bins were given, and the doubled ranks of 2^32 bins or more sum past 2^64".format(nbins))
+
+
 def moments(vectors, device=0):
     """-> (sums: list[int], gram: n x n list of Python ints), exact, computed on the device.
 
     `vectors`: any mix of Engine objects (synced; their table is used in place, never copied), torch int64/uint64 tensors on that
     device, and host uint64 numpy arrays (uploaded for the call, freed after it).  ValueError if the lengths differ; KdbHipError
     without a device."""
-    from .engine import Engine
     _require_device(device)
     vectors = list(vectors)
     if not vectors:
         raise ValueError("moments needs at least one vector")
     keep, ptrs, lengths = [], [], []
-    torch = None
     for v in vectors:
-        if isinstance(v, Engine):
-            if v.device != int(device):
-                raise ValueError("an engine on device {0} was given, device {1} asked".format(v.device, device))
-            v.sync()
-            p, nb = v.table_ptr()
-        elif isinstance(v, np.ndarray):
-            if v.dtype != np.uint64 or v.ndim != 1:
-                raise ValueError("host vectors must be one-dimensional uint64 arrays")
-            import torch
-            t = torch.from_numpy(np.ascontiguousarray(v).view(np.int64)).to("cuda:{0}".format(int(device)))
-            keep.append(t)
-            p, nb = t.data_ptr(), t.numel()
-        else:
-            import torch
-            if not isinstance(v, torch.Tensor):
-                raise TypeError("vectors are Engine objects, torch tensors or numpy arrays, not {0}".format(type(v).__name__))
-            if v.dtype not in (torch.int64, torch.uint64) or v.dim() != 1 or not v.is_contiguous():
-                raise ValueError("device vectors must be contiguous one-dimensional int64/uint64 tensors")
-            if v.device.type != "cuda" or v.device.index != int(device):
-                raise ValueError("a tensor on {0} was given, device {1} asked".format(v.device, device))
-            keep.append(v)
-            p, nb = v.data_ptr(), v.numel()
+        p, nb, owner = _device_vector(v, device)
+        keep.append(owner)
         ptrs.append(p)
-        lengths.append(int(nb))
+        lengths.append(nb)
     if len(set(lengths)) != 1:
         raise ValueError("the vectors differ in length: {0}".format(sorted(set(lengths))))
-    if torch is not None:
+    if any(o is not None for o in keep):
+        import torch
         torch.cuda.synchronize(int(device))              # (uploads and whatever produced the tensors: kdb_gram runs on a stream of its own)
     s, G, _ = gram(ptrs, lengths[0], device)
     del keep
@@ -139,15 +171,45 @@ def from_moments(sums, gram, nbins, metric):
     return out
 
 
-def distance_matrix(vectors, metric="correlation", device=0):
-    """moments() on the device, then from_moments()."""
-    if metric not in METRICS:
-        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+def rank_vectors(vectors, device=0):
+    """The doubled mid-ranks of every vector, as device tensors (spectrum.ranks).  An engine's table and a caller's tensor are left as
+    they are and a host array is uploaded, so n rank vectors are needed: MemoryError, before any device work, if they do not fit the
+    free device memory."""
+    from . import spectrum
     vectors = list(vectors)
+    if not vectors:
+        raise ValueError("rank_vectors needs at least one vector")
+    lengths = sorted(set(_length(v) for v in vectors))
+    if len(lengths) != 1:
+        raise ValueError("the vectors differ in length: {0}".format(lengths))
+    _check_rank_bins(lengths[0])
+    _require_device(device)
+    import torch
+    need = 8 * lengths[0] * len(vectors)
+    free_b, _ = torch.cuda.mem_get_info(int(device))
+    if need > free_b:
+        raise MemoryError("the rank vectors of {0} profiles of {1} bins need {2} bytes of device memory, {3} are free".format(
+            len(vectors), lengths[0], need, free_b))
+    return [spectrum.ranks(v, device=device) for v in vectors]
+
+
+def distance_matrix(vectors, metric="correlation", device=0):
+    """moments() on the device, then from_moments(); for `spearman` the device ranks the vectors first (rank_vectors) and the moments are
+    those of the ranks."""
+    _check_metric(metric)
+    vectors = list(vectors)
+    if metric in RANK_METRICS:
+        vectors, metric = rank_vectors(vectors, device=device), "pearson"
     s, G = moments(vectors, device=device)
-    v0 = vectors[0]
-    nbins = v0.nbins if hasattr(v0, "nbins") else (v0.size if isinstance(v0, np.ndarray) else v0.numel())
-    return from_moments(s, G, nbins, metric)
+    return from_moments(s, G, _length(vectors[0]), metric)
+
+
+def spearman(x, y, device=0):
+    """Spearman's rho of two count vectors (the reference's python_distances.spearman, :95-114, which calls scipy.stats.spearmanr): exact
+    Pearson's r of their mid-ranks, ties sharing the mean of their ranks as scipy ranks them; nan if either vector is constant.
+    -> rho alone: the p-value the reference returns beside it (and drops, __init__.py:735-738) is not reproduced."""
+    vecs = [np.ascontiguousarray(v, dtype=np.uint64) if isinstance(v, (np.ndarray, list, tuple)) else v for v in (x, y)]
+    return float(distance_matrix(vecs, "spearman", device=device)[0][1])
 
 
 def correlation(a, b, total_kmers):
@@ -191,8 +253,7 @@ def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None
     print the matrix.  -> the matrix."""
     from . import fileutil
     inputs = list(inputs)
-    if metric not in METRICS:
-        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+    _check_metric(metric)
     if len(inputs) < 2:
         raise ValueError("'kmerdb distance' requires more than one .kdb file as positional inputs")
     if not all(os.path.splitext(p)[-1] == ".kdb" for p in inputs):
@@ -210,14 +271,16 @@ def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None
 
 def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not_canonicalize=False, device=0):
     """Count the files of a samplesheet and compare their profiles without leaving HBM: one engine counts each file, its vector is copied
-    device-to-device into row i of one n x 4^k tensor, the engine is reset; then one moments() call.  MemoryError before counting if
+    device-to-device into row i of one n x 4^k tensor, the engine is reset; then one moments() call (for `spearman` the rows are ranked in
+    place first: no further memory).  MemoryError before counting if
     n * 8 * 4^k plus one engine does not fit the free device memory.  -> (matrix, columns, per-file metadata)."""
     from . import parse
     from .engine import Engine, KDB_N_DROP, KDB_N_EXPAND
     if type(k) is not int:
         raise TypeError("k must be an int")
-    if metric not in METRICS:
-        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS)))
+    _check_metric(metric)
+    if metric in RANK_METRICS:
+        _check_rank_bins(4 ** k)
     files = list(files)
     if not files:
         raise ValueError("profile_distances needs at least one file")
@@ -237,5 +300,10 @@ def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not
             rows[i].copy_(eng.table_tensor())
             torch.cuda.synchronize(int(device))
             eng.reset()
+    if metric in RANK_METRICS:                                               # the rows are this function's own: ranked where they lie
+        from . import spectrum
+        for i in range(n):
+            spectrum.ranks(rows[i], out=rows[i], device=device)
+        metric = "pearson"
     s, G = moments([rows[i] for i in range(n)], device=device)
     return from_moments(s, G, N, metric), column_names_for(files), metadata

@@ -187,7 +187,7 @@ def profile(inputs, k, output_name, no_ambiguous=False, do_not_canonicalize=Fals
 
 def main(argv=None):
     """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
-    `graph` and `distance <metric> a.kdb b.kdb ...` beside it."""
+    `graph`, `distance <metric> a.kdb b.kdb ...` and `spectrum a.kdb ...` beside it."""
     import argparse
     ap = argparse.ArgumentParser(prog="kmerdb_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -210,12 +210,23 @@ def main(argv=None):
     gp.add_argument("input", nargs="+")
     gp.add_argument("kdbg")
     dp = sub.add_parser("distance", help="distance matrix of two or more .kdb count profiles (__init__.py:577-813)")
-    dp.add_argument("metric", choices=["pearson", "correlation", "cosine", "sqeuclidean", "euclidean"])
+    dp.add_argument("metric", choices=["pearson", "spearman", "correlation", "cosine", "sqeuclidean", "euclidean"])
     dp.add_argument("--column-names", default=None, help="a file with one column name per line (default: the inputs' basenames)")
     dp.add_argument("--output-delimiter", default="\t")
     dp.add_argument("--device", type=int, default=0)
     dp.add_argument("input", nargs="+")
+    sp = sub.add_parser("spectrum", help="abundance spectrum of .kdb count profiles: `count<TAB>bins` rows, the counts that occur, ascending")
+    sp.add_argument("--device", type=int, default=0)
+    sp.add_argument("input", nargs="+")
     a = ap.parse_args(argv)
+    if a.cmd == "spectrum":
+        from . import spectrum
+        for p in a.input:
+            if len(a.input) > 1:
+                print("# {0}".format(p))
+            values, mult = spectrum.spectrum(fileutil.read_kdb(p).counts, device=a.device)
+            sys.stdout.write("".join("{0}\t{1}\n".format(v, n) for v, n in zip(values.tolist(), mult.tolist())))
+        return 0
     if a.cmd == "distance":
         from . import distance
         distance.distances(a.input, a.metric, column_names=a.column_names, output_delimiter=a.output_delimiter, device=a.device)

@@ -2,6 +2,8 @@
 import hashlib
 import os
 
+import numpy as np
+
 
 def checksum(filepath):
     """md5 and sha256 of the raw (possibly gzipped) file bytes -- kmerdb/util.py:35-50."""
@@ -118,6 +120,30 @@ def effective_cpus():
     if q is not None:
         n = min(n, max(1, int(q + 0.999)))
     return max(1, n)
+
+
+HISTO_MAX_ENTRIES = 1 << 27            # get_histo: the longest list it builds (a Python list of 2^27 ints is 1 GiB of pointers alone)
+
+
+def get_histo(counts):
+    """kmerdb/util.py:92-116, drop-in: a list of length max(counts) + 1 whose entry c is the number of bins that hold c -- for c > 2 only,
+    entries 0..2 stay 0 as the reference leaves them (util.py:114).  The tally is spectrum.spectrum()'s, on the device, not a Python
+    loop over the bins.  ValueError if the list would pass HISTO_MAX_ENTRIES entries (one repeat k-mer counted 10^9 times asks the
+    reference for a list of 10^9 zeros): spectrum() returns the same numbers as (values, multiplicities)."""
+    if type(counts) is not list:
+        raise TypeError("kmerdb_amd.util.get_histo takes a list as its positional argument")
+    from . import spectrum
+    values, mult = spectrum.spectrum(np.array(counts, dtype="uint64"))
+    count_max = int(values[-1])
+    if count_max + 1 > HISTO_MAX_ENTRIES:
+        raise ValueError("the largest count is {0}: a histogram list of {1} entries is not built (more than {2}); "
+                         "kmerdb_amd.spectrum.spectrum() gives the values that occur and their multiplicities".format(
+                             count_max, count_max + 1, HISTO_MAX_ENTRIES))
+    hist = [0] * (count_max + 1)
+    for v, n in zip(values.tolist(), mult.tolist()):
+        if v > 2:
+            hist[v] = n
+    return hist
 
 
 def is_gz_file(filepath):
