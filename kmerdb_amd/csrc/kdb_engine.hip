@@ -517,8 +517,18 @@ int check_errors(kdb_engine *e)
                     c.n_short, e->k);
     if (c.bad_layout)
         return fail(KDB_ERR_ARG, "read_offsets must rise from 0 to nbytes (records tile the residue buffer exactly)");
-    if (c.internal_err)
+    if (c.internal_err) {
+        // Besides the page sequences (and the level-2 kernel's checks) a side list of the overlapped path raises this counter when it takes more pairs than
+        // it has room for (hot_add).  Where a list's header still shows that -- it is written anew when a later batch uses the list -- say so: the
+        // lists are sized from their batches (scatter_count_overlapped), so it means that the bound there is wrong, not that the input is.
+        for (int q = 0; q < 2; q++) {
+            unsigned long long hd[2] = {0, 0};
+            if (e->ov.side[q] && hipMemcpy(hd, e->ov.side[q], sizeof hd, hipMemcpyDeviceToHost) == hipSuccess && hd[0] > hd[1])
+                return fail(KDB_ERR_STATE, "internal: the overlapped path's side list of degenerate ids overflowed (%llu pairs for %llu places); counts are incomplete",
+                            hd[0], hd[1]);
+        }
         return fail(KDB_ERR_STATE, "internal: a scatter kernel ran out of its page sequence (%llu times); counts are incomplete", c.internal_err);
+    }
     if (c.not_uniform)
         return fail(KDB_ERR_ARG, "kdb_submit_device_const needs records of one length (the buffer is never marked); use kdb_submit_device");
     if (c.n_bad)

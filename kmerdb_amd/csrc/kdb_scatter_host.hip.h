@@ -328,15 +328,21 @@ inline int scatter_count_overlapped(OverlapState &ov, const PagedOptions &opt, h
     }
     // this set's pages are read by the pass of the batch before last: the scatter stream waits for it (and a reallocation drains it)
     if (ov.used[j] && hipStreamWaitEvent(s_scatter, ov.hist_done[j], 0) != hipSuccess) { partition_error_ref() = "stream wait failed"; return 1; }
-    const size_t npages = sub_batch(g, 0, 0).npages, side_need = (size_t)g.Gmax * SC_HOT + 65536;
+    // The side list takes one pair per degenerate group that finds its slot of the workgroup's table taken, and one per slot at the end of the
+    // kernel.  A group is at most one per wave and window slot: sixteen per wave of 64 chunks and tile -- nbytes / 64 and a little for the tiles'
+    // last chunks --, so the list is sized from the batch (a fixed 65536 on top of the drain's pairs overflowed on a few MB of short-period repeats
+    // with many distinct units).  The largest batch that comes this far -- one sub-batch, 2 Gi positions -- makes 2^25 pairs: 512 MiB a list.
+    const size_t npages = sub_batch(g, 0, 0).npages;
+    const size_t side_need = (size_t)g.ntiles_all * (g.tile_pos / 16u + 1u) / 4u + (size_t)g.Gmax * SC_HOT;
     if ((st.cap < npages || st.bkt_cap < (size_t)g.nb) && ov.used[j] && hipEventSynchronize(ov.hist_done[j]) != hipSuccess) return reserve_error(1);
     { const int rc = scatter_reserve(st, s_scatter, npages, (size_t)g.nb); if (rc) return rc; }
     if (ov.side_cap < side_need) {
+        const size_t side_new = side_need + side_need / 4;                // (grow-only, with headroom: a reallocation drains both passes)
         for (int q = 0; q < 2; q++) {
             if (ov.side[q]) { if (ov.used[q] && hipEventSynchronize(ov.hist_done[q]) != hipSuccess) return reserve_error(1); (void)hipFree(ov.side[q]); ov.side[q] = nullptr; }
-            if (hipMalloc((void **)&ov.side[q], (2 + 2 * side_need) * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); ov.side_cap = 0; return reserve_error(2); }
+            if (hipMalloc((void **)&ov.side[q], (2 + 2 * side_new) * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); ov.side_cap = 0; return reserve_error(2); }
         }
-        ov.side_cap = side_need;
+        ov.side_cap = side_new;
     }
     hipLaunchKernelGGL(hot_side_kernel, dim3(1), dim3(1), 0, s_scatter, B.d_ctr, ov.side[j], (unsigned long long)ov.side_cap);
     ScLaunch L;
