@@ -194,6 +194,48 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
              double   *kernel_ms_out /* may be NULL: device time by HIP events */);
 
 /*
+ * What the distances that are not functions of the moments need, as exact integers, in one pairwise sweep of the same n vectors
+ * (csrc/kdb_pairstats.hip.h): cityblock, chebyshev, braycurtis, hamming and the presence/absence family (kmerdb_amd/distance.py).
+ *   S[i]   = Sum_b x_i[b]                    -> sums_out[2 i], [2 i + 1] = low, high 64 bits
+ *   nnz[i] = #{b : x_i[b] > 0}               -> nnz_out[i]
+ *   for every pair, at [i n + j] and [j n + i] alike (both triangles are filled):
+ *   L1     = Sum_b |x_i[b] - x_j[b]|         -> l1_out[2 (i n + j)], [.. + 1] = low, high 64 bits
+ *   Linf   = max_b |x_i[b] - x_j[b]|         -> linf_out[i n + j]
+ *   ne     = #{b : x_i[b] != x_j[b]}         -> ne_out[i n + j]
+ *   both   = #{b : x_i[b] > 0 and x_j[b] > 0} -> both_out[i n + j]
+ *   on the diagonal L1 = Linf = ne = 0 and both = nnz[i].
+ * d_vectors, the call's conventions and its refusals are those of the moments above: n device pointers to nbins uint64 each, 16-byte
+ * aligned, read only, the same pointer may appear twice; synchronous; scratch allocated and freed inside the call.
+ * L1 <= S[i] + S[j] < 2^65 once every S is below 2^64: it may pass one word, so it has two.  KDB_ERR_ARG: n < 1, n > KDB_GRAM_MAX,
+ * nbins == 0 or above 2^36, a NULL or misaligned pointer, a NULL output, or some S[i] >= 2^64.  KDB_ERR_NOMEM: the scratch does not fit.
+ * kernel_ms_out (may be NULL): device time of the sweep, by HIP events.
+ * KDB_PAIRSTATS_BLOCK / _HALF / _WG_BINS: the kernel's constants -- vectors per register block, vectors of the second block a row takes
+ * off the diagonal, bins one workgroup covers per grid stride.
+ */
+#define KDB_PAIRSTATS_BLOCK 4
+#define KDB_PAIRSTATS_HALF 2
+#define KDB_PAIRSTATS_WG_BINS 512
+int kdb_pairstats(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
+                  uint64_t *sums_out  /* 2*n   words */, uint64_t *nnz_out  /* n   words */,
+                  uint64_t *l1_out    /* 2*n*n words */, uint64_t *linf_out /* n*n words */,
+                  uint64_t *ne_out    /* n*n   words */, uint64_t *both_out /* n*n words */,
+                  double   *kernel_ms_out /* may be NULL */);
+
+/*
+ * The two pairwise sums that need a quotient or a logarithm per bin, in float64 (csrc/kdb_pairstats.hip.h), for every pair i != j:
+ *   C = Sum_b |x - y| / (x + y) over the bins with x + y > 0                        -> canberra_out[i n + j]    (scipy's canberra)
+ *   D = Sum_b [ p ln(p/m) + q ln(q/m) ], p = x/S[i], q = y/S[j], m = (p + q)/2      -> js_out[i n + j]          (scipy's jensenshannon is sqrt(D/2))
+ * a zero p or q contributes 0; D is nan where S[i] or S[j] is 0; the diagonal of both is 0; both triangles are filled.
+ * |x - y| is formed in integers; S are the exact sums (one integer sweep inside the call), converted to float64 once.  Each per-bin
+ * term is non-negative and is formed before it is added; no atomics; the grid depends on nbins alone and the order of the additions is
+ * fixed: two calls on the same vectors return the same bits (on one build; not promised across builds).  IEEE division: the library is
+ * built without fast-math.  Conventions and refusals as above.  kernel_ms_out (may be NULL): device time of the float sweep alone.
+ */
+int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
+                  double *canberra_out /* n*n */, double *js_out /* n*n */,
+                  double *kernel_ms_out /* may be NULL */);
+
+/*
  * The abundance spectrum of one finished count vector -- how many bins hold each count value -- in one sweep on the device
  * (csrc/kdb_spectrum.hip.h): the reference's util.get_histo (kmerdb/util.py:92-116), and what a rank transform starts from.
  *   dense_out[v]     = number of bins that hold v, for v < KDB_SPECTRUM_DENSE; exact uint64 (at k = 17 the entry of 0 passes 2^32)

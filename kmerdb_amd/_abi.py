@@ -19,6 +19,7 @@ KDB_SUBMIT_PINNED, KDB_SUBMIT_CONTINUES = 1, 2
 KDB_N_KERNELS = 8
 KDB_GRAM_MAX, KDB_GRAM_BLOCK, KDB_GRAM_WG_BINS = 64, 4, 512
 KDB_SPECTRUM_DENSE, KDB_SPECTRUM_WG_BINS = 65536, 1024
+KDB_PAIRSTATS_BLOCK, KDB_PAIRSTATS_HALF, KDB_PAIRSTATS_WG_BINS = 4, 2, 512
 ABI_VERSION = 6
 
 # every symbol include/kdbhip.h declares: (name, restype, argtypes)
@@ -46,6 +47,10 @@ SYMBOLS = (
     ("kdb_reduce", ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_int]),
     ("kdb_gram", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_uint64, _u64p, _u64p,
                                 ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_pairstats", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_uint64, _u64p, _u64p, _u64p, _u64p, _u64p, _u64p,
+                                     ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_pairfloat", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double),
+                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
     ("kdb_spectrum", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, _u64p, _u64p, ctypes.c_uint64, _u64p, ctypes.POINTER(ctypes.c_double)]),
     ("kdb_rank_transform", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_double)]),
     ("kdb_strand_merge", ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int]),

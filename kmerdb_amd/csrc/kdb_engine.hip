@@ -4,6 +4,7 @@
 // needs the device fails with KDB_ERR_HIP if HIP cannot provide one.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstddef>
 #include <cstdio>
@@ -23,6 +24,7 @@
 #include "kdb_smallk.hip.h"
 #include "kdb_probe.hip.h"
 #include "kdb_gram.hip.h"
+#include "kdb_pairstats.hip.h"
 #include "kdb_spectrum.hip.h"
 #include "kdb_spectrum_host.cpp.h"
 #include "kdb_strands.hip.h"
@@ -1280,6 +1282,219 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
     for (int i = 0; i < n; i++)
         if (sums_out[2 * i + 1] != 0)
             return fail(KDB_ERR_ARG, "kdb_gram: the sum of vector %d is 2^64 or more: its products may have wrapped 128 bits", i);
+    return KDB_OK;
+}
+
+// ---- the pairwise statistics that are not moments (kdb_pairstats.hip.h): exact integers, and the float sweep of canberra / jensenshannon ----
+namespace {
+
+int pair_check_args(const char *who, const void *const *d_vectors, int n, uint64_t nbins)
+{
+    if (n < 1 || n > KDB_GRAM_MAX) return fail(KDB_ERR_ARG, "%s: n=%d, 1..%d vectors supported", who, n, KDB_GRAM_MAX);
+    if (nbins == 0 || nbins > kdbpair::NBINS_MAX) return fail(KDB_ERR_ARG, "%s: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)", who);
+    if (!d_vectors) return fail(KDB_ERR_ARG, "%s: d_vectors must not be NULL", who);
+    for (int i = 0; i < n; i++) {
+        if (!d_vectors[i]) return fail(KDB_ERR_ARG, "%s: vector %d is NULL", who, i);
+        if (((uintptr_t)d_vectors[i] & 15u) != 0) return fail(KDB_ERR_ARG, "%s: vector %d is not 16-byte aligned", who, i);
+    }
+    return KDB_OK;
+}
+
+struct PairGroup { uint32_t row0, nrows; int na, nb; bool diag; };
+
+void pair_launch(const PairGroup &gr, uint32_t gx, const unsigned long long *const *vecs, const kdbpair::Row *rows, uint32_t nchunks, uint32_t pstride,
+                 unsigned long long *partials, hipStream_t st)
+{
+    const dim3 grid(gx, gr.nrows), block(kdbpair::TPB);
+    const kdbpair::Row *r = rows + gr.row0;
+    unsigned long long *p = partials + (uint64_t)gr.row0 * pstride * kdbpair::ROW_WORDS;
+#define KDB_PAIR_CASE(NA, NB, DIAG) hipLaunchKernelGGL((kdbpair::pair_kernel<NA, NB, DIAG>), grid, block, 0, st, vecs, r, nchunks, pstride, p)
+    if (gr.diag) {
+        switch (gr.na) {
+            case 1: KDB_PAIR_CASE(1, 1, true); break;
+            case 2: KDB_PAIR_CASE(2, 2, true); break;
+            case 3: KDB_PAIR_CASE(3, 3, true); break;
+            default: KDB_PAIR_CASE(4, 4, true); break;
+        }
+    } else {                                           // (off the diagonal the first block is always a full one)
+        if (gr.nb == 1) KDB_PAIR_CASE(4, 1, false);
+        else KDB_PAIR_CASE(4, 2, false);
+    }
+#undef KDB_PAIR_CASE
+}
+
+struct PairScratch {
+    const unsigned long long **vecs = nullptr; void *rows = nullptr, *partials = nullptr, *out = nullptr; double *sums = nullptr;
+    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
+    ~PairScratch()
+    {
+        (void)hipFree(vecs); (void)hipFree(rows); (void)hipFree(partials); (void)hipFree(out); (void)hipFree(sums);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+}  // namespace
+
+int kdb_pairstats(int device_id, const void *const *d_vectors, int n, uint64_t nbins, uint64_t *sums_out, uint64_t *nnz_out, uint64_t *l1_out,
+                  uint64_t *linf_out, uint64_t *ne_out, uint64_t *both_out, double *kernel_ms_out)
+{
+    constexpr int B = kdbpair::B, HALF = kdbpair::HALF, NPAIR = kdbpair::NPAIR, PW = kdbpair::PAIR_WORDS, VW = kdbpair::VEC_WORDS, RW = kdbpair::ROW_WORDS;
+    if (int rc = pair_check_args("kdb_pairstats", d_vectors, n, nbins)) return rc;
+    if (!sums_out || !nnz_out || !l1_out || !linf_out || !ne_out || !both_out) return fail(KDB_ERR_ARG, "kdb_pairstats: the six output arrays must not be NULL");
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    DeviceGuard g(device_id);
+
+    // rows, grouped by the kernel that serves them: the diagonal blocks (the last may hold fewer than B vectors), then every earlier block
+    // against the later blocks' vectors, HALF at a time
+    const int nblk = (n + B - 1) / B;
+    auto block_size = [&](int b) { return std::min(B, n - b * B); };
+    std::vector<kdbpair::Row> rows;
+    std::vector<PairGroup> groups;
+    auto push = [&](int a0, int na, int b0, int nb) {
+        const bool diag = a0 == b0;
+        if (groups.empty() || groups.back().na != na || groups.back().nb != nb || groups.back().diag != diag)
+            groups.push_back(PairGroup{(uint32_t)rows.size(), 0, na, nb, diag});
+        groups.back().nrows++;
+        rows.push_back(kdbpair::Row{(uint8_t)a0, (uint8_t)na, (uint8_t)b0, (uint8_t)nb});
+    };
+    for (int b = 0; b < nblk; b++) push(b * B, block_size(b), b * B, block_size(b));
+    for (int pass = 0; pass < 2; pass++)               // (rows of HALF vectors first, then the rows of a single one: two groups at most)
+        for (int bj = 1; bj < nblk; bj++)
+            for (int h = 0; h < block_size(bj); h += HALF) {
+                const int nb = std::min(HALF, block_size(bj) - h);
+                if ((nb == HALF) != (pass == 0)) continue;
+                for (int bi = 0; bi < bj; bi++) push(bi * B, B, bj * B + h, nb);
+            }
+    const uint32_t nrows = (uint32_t)rows.size();
+    // pair_kernel takes the whole chunks, pair_tail_kernel the bins behind them; a row's partials: one per workgroup, then the tail's
+    const uint32_t nchunks = (uint32_t)(nbins / kdbpair::CHUNK_BINS), wg_chunks = kdbpair::TPB / 64;
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, nrows <= 3 ? 1024u : 256u));       // (any grid gives the same integers)
+    const uint32_t nparts = gx + 1;
+    PairScratch sc;
+    std::vector<const unsigned long long *> ptrs((size_t)n);
+    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
+    if (hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess || hipMalloc(&sc.rows, nrows * sizeof(kdbpair::Row)) != hipSuccess ||
+        hipMalloc(&sc.partials, (uint64_t)nrows * nparts * RW * sizeof(uint64_t)) != hipSuccess ||
+        hipMalloc(&sc.out, (uint64_t)nrows * RW * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_pairstats: no room for the partial records of %u x %u workgroups", nrows, gx);
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&sc.a));
+    HIP_TRY(hipEventCreate(&sc.b));
+    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.rows, rows.data(), nrows * sizeof(kdbpair::Row), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    for (const PairGroup &gr : groups)
+        pair_launch(gr, gx, sc.vecs, (const kdbpair::Row *)sc.rows, nchunks, nparts, (unsigned long long *)sc.partials, sc.st);
+    hipLaunchKernelGGL(kdbpair::pair_tail_kernel, dim3(nrows), dim3(64), 0, sc.st, sc.vecs, (const kdbpair::Row *)sc.rows, (uint64_t)nchunks * kdbpair::CHUNK_BINS, nbins,
+                       nparts, gx, (unsigned long long *)sc.partials);
+    hipLaunchKernelGGL(kdbpair::pair_combine_kernel, dim3(nrows), dim3(256), 0, sc.st, (const unsigned long long *)sc.partials, nparts, (unsigned long long *)sc.out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    std::vector<unsigned long long> res((size_t)nrows * RW);
+    HIP_TRY(hipMemcpyAsync(res.data(), sc.out, res.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    if (kernel_ms_out) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
+        *kernel_ms_out = (double)ms;
+    }
+    for (uint32_t r = 0; r < nrows; r++) {
+        const unsigned long long *rec = &res[(size_t)r * RW];
+        const kdbpair::Row &row = rows[r];
+        const bool diag = row.a0 == row.b0;
+        for (int i = 0; i < row.na; i++) {
+            const size_t vi = (size_t)row.a0 + i;
+            if (diag) {
+                const unsigned long long *v = rec + NPAIR * PW + i * VW;
+                sums_out[2 * vi] = v[0]; sums_out[2 * vi + 1] = v[1]; nnz_out[vi] = v[2];
+                l1_out[2 * (vi * n + vi)] = l1_out[2 * (vi * n + vi) + 1] = linf_out[vi * n + vi] = ne_out[vi * n + vi] = 0;
+                both_out[vi * n + vi] = v[2];
+            }
+            for (int j = diag ? i + 1 : 0; j < row.nb; j++) {
+                const size_t vj = (size_t)row.b0 + j, at = vi * n + vj, ta = vj * n + vi;
+                const unsigned long long *p = rec + (i * B + j) * PW;
+                l1_out[2 * at] = l1_out[2 * ta] = p[0];
+                l1_out[2 * at + 1] = l1_out[2 * ta + 1] = p[1];
+                linf_out[at] = linf_out[ta] = p[2];
+                ne_out[at] = ne_out[ta] = p[3];
+                both_out[at] = both_out[ta] = p[4];
+            }
+        }
+    }
+    for (int i = 0; i < n; i++)
+        if (sums_out[2 * i + 1] != 0)
+            return fail(KDB_ERR_ARG, "kdb_pairstats: the sum of vector %d is 2^64 or more: L1 of a pair with it may not fit its two words", i);
+    return KDB_OK;
+}
+
+int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t nbins, double *canberra_out, double *js_out, double *kernel_ms_out)
+{
+    constexpr int FW = kdbpair::FLOAT_WORDS;
+    if (int rc = pair_check_args("kdb_pairfloat", d_vectors, n, nbins)) return rc;
+    if (!canberra_out || !js_out) return fail(KDB_ERR_ARG, "kdb_pairfloat: canberra_out and js_out must not be NULL");
+    // the exact sums (and the refusal of one that reaches 2^64), from the integer sweep
+    const size_t nn = (size_t)n * n;
+    std::vector<uint64_t> isums(2 * (size_t)n), scratch64(6 * nn + n);
+    if (int rc = kdb_pairstats(device_id, d_vectors, n, nbins, isums.data(), scratch64.data() + 6 * nn, scratch64.data(), scratch64.data() + 2 * nn,
+                               scratch64.data() + 3 * nn, scratch64.data() + 4 * nn, nullptr))
+        return rc;
+    std::vector<double> sums((size_t)n);
+    for (int i = 0; i < n; i++) sums[i] = (double)isums[2 * i];                       // (one rounding; the high word is zero)
+    for (size_t i = 0; i < nn; i++) canberra_out[i] = js_out[i] = 0.0;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (n < 2) return KDB_OK;
+    DeviceGuard g(device_id);
+
+    std::vector<kdbpair::FloatRow> rows;
+    for (int i = 0; i < n; i++) for (int j = i + 1; j < n; j++) rows.push_back(kdbpair::FloatRow{(uint8_t)i, (uint8_t)j});
+    const uint32_t nrows = (uint32_t)rows.size();
+    const uint32_t nchunks = (uint32_t)(nbins / kdbpair::CHUNK_BINS), wg_chunks = kdbpair::TPB / 64;
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, 512u));          // (a function of nbins alone: the order of the additions is fixed)
+    const uint32_t nparts = gx + 1;
+    PairScratch sc;
+    std::vector<const unsigned long long *> ptrs((size_t)n);
+    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
+    if (hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess || hipMalloc(&sc.rows, nrows * sizeof(kdbpair::FloatRow)) != hipSuccess ||
+        hipMalloc((void **)&sc.sums, sums.size() * sizeof(double)) != hipSuccess ||
+        hipMalloc(&sc.partials, (uint64_t)nrows * nparts * FW * sizeof(double)) != hipSuccess ||
+        hipMalloc(&sc.out, (uint64_t)nrows * FW * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_pairfloat: no room for the partial sums of %u x %u workgroups", nrows, gx);
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&sc.a));
+    HIP_TRY(hipEventCreate(&sc.b));
+    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.rows, rows.data(), nrows * sizeof(kdbpair::FloatRow), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.sums, sums.data(), sums.size() * sizeof(double), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    hipLaunchKernelGGL(kdbpair::pairfloat_kernel, dim3(gx, nrows), dim3(kdbpair::TPB), 0, sc.st, sc.vecs, (const kdbpair::FloatRow *)sc.rows, (const double *)sc.sums, nchunks,
+                       nparts, (double *)sc.partials);
+    hipLaunchKernelGGL(kdbpair::pairfloat_tail_kernel, dim3(nrows), dim3(64), 0, sc.st, sc.vecs, (const kdbpair::FloatRow *)sc.rows, (const double *)sc.sums,
+                       (uint64_t)nchunks * kdbpair::CHUNK_BINS, nbins, nparts, gx, (double *)sc.partials);
+    hipLaunchKernelGGL(kdbpair::pairfloat_combine_kernel, dim3(nrows), dim3(64), 0, sc.st, (const double *)sc.partials, nparts, (double *)sc.out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    std::vector<double> res((size_t)nrows * FW);
+    HIP_TRY(hipMemcpyAsync(res.data(), sc.out, res.size() * sizeof(double), hipMemcpyDeviceToHost, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    if (kernel_ms_out) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
+        *kernel_ms_out = (double)ms;
+    }
+    for (uint32_t r = 0; r < nrows; r++) {
+        const size_t i = rows[r].i, j = rows[r].j;
+        const bool empty = isums[2 * i] == 0 || isums[2 * j] == 0;
+        canberra_out[i * n + j] = canberra_out[j * n + i] = res[(size_t)r * FW];
+        js_out[i * n + j] = js_out[j * n + i] = empty ? (double)NAN : res[(size_t)r * FW + 1];
+    }
     return KDB_OK;
 }
 

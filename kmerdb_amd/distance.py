@@ -1,9 +1,22 @@
-"""kmerdb_amd.distance -- `kmerdb distance` on count profiles (reference kmerdb/__init__.py:577-813, distance.pyx:108-152).
+"""kmerdb_amd.distance -- `kmerdb distance` on count profiles (reference kmerdb/__init__.py:577-813, :2314-2338, distance.pyx:108-152).
 
-Every metric the reference offers on count profiles is a function of the vectors' sums S[i], their Gram matrix
-G[i][j] = Sum_b x_i[b] x_j[b] and the number of bins N.  The device computes those as exact 128-bit integers in one sweep of the
-vectors where they lie in HBM (kdb_gram, csrc/kdb_gram.hip.h); the host does the last step in exact integer / 150-digit decimal
-arithmetic, so every value is the float64 nearest the true one, or its neighbour.  No CPU fallback: without a device moments() raises.
+The moment metrics (METRICS: correlation, pearson, cosine, euclidean, sqeuclidean; `minkowski` is euclidean, scipy's default p = 2) are
+functions of the vectors' sums S[i], their Gram matrix G[i][j] = Sum_b x_i[b] x_j[b] and the number of bins N.  The device computes those
+as exact 128-bit integers in one sweep of the vectors where they lie in HBM (kdb_gram, csrc/kdb_gram.hip.h); the host does the last step
+in exact integer / 150-digit decimal arithmetic, so every value is the float64 nearest the true one, or its neighbour.  No CPU fallback:
+without a device moments() raises.
+
+The other metrics people use on count profiles are NOT functions of the moments.  SWEEP_METRICS (cityblock, chebyshev, braycurtis,
+hamming / matching and the presence/absence family: jaccard, dice, rogerstanimoto, sokalmichener, russellrao, sokalsneath, yule, kulsinski)
+are functions of a second set of exact integers -- per vector S and nnz = #{x > 0}, per pair L1 = Sum |x - y|, Linf = max |x - y|,
+ne = #{x != y}, both = #{x > 0 and y > 0} -- which kdb_pairstats makes in one pairwise sweep (csrc/kdb_pairstats.hip.h);
+from_pairstats() does the last step in fractions.  FLOAT_METRICS (canberra, jensenshannon) need a quotient or a logarithm per bin: the
+float64 sweep kdb_pairfloat, run only when one of the two is asked for.
+
+The presence/absence family is defined on x > 0, which is what scipy computes for jaccard, rogerstanimoto, russellrao, sokalmichener,
+sokalsneath and yule on integer input.  Departure from scipy, on purpose: its `dice` on raw counts multiplies the counts and returns a
+number without meaning (it can be negative); ours is dice of the presence vectors, i.e. scipy's on `x > 0`.  `kulsinski` follows
+scipy <= 1.11's documented formula (later versions dropped the name; the reference still lists it).
 
 Departure from the reference, on purpose: its custom `pearson` (distance.pyx:118-119) rounds both means to float32 before it forms the
 residuals; here the means never exist -- num = N Gxy - Sx Sy is an integer.  `correlation` is scipy's 1 - r, the reference CLI's default.
@@ -14,6 +27,7 @@ the same exact path runs on the rank vectors.  k <= 15: the doubled ranks of N b
 """
 import ctypes
 import decimal
+import fractions
 import os
 import sys
 
@@ -25,6 +39,12 @@ METRICS = ("pearson", "correlation", "cosine", "sqeuclidean", "euclidean")
 RANK_METRICS = ("spearman",)                                                         # Pearson's r of the vectors' ranks: the device ranks first
 RANK_MAX_BINS = 1 << 32                                                              # kdb_rank_transform refuses this many bins and more
 IDENTITY = {"pearson": 1.0, "correlation": 0.0, "cosine": 0.0, "sqeuclidean": 0.0, "euclidean": 0.0}     # python_distances.identity
+SWEEP_METRICS = ("cityblock", "chebyshev", "braycurtis", "hamming", "matching", "jaccard", "dice", "rogerstanimoto", "sokalmichener",
+                 "russellrao", "sokalsneath", "yule", "kulsinski")                  # functions of kdb_pairstats' integers
+FLOAT_METRICS = ("canberra", "jensenshannon")                                        # the float64 sweep, kdb_pairfloat
+ALIAS_METRICS = {"minkowski": "euclidean"}                                           # scipy's default p = 2: the moment path
+SWEEP_IDENTITY = dict((m, 0.0) for m in SWEEP_METRICS + FLOAT_METRICS)
+ALL_METRICS = METRICS + RANK_METRICS + SWEEP_METRICS + FLOAT_METRICS + tuple(ALIAS_METRICS)
 _CTX = decimal.Context(prec=150, Emax=decimal.MAX_EMAX, Emin=decimal.MIN_EMIN)       # vx * vy < 2^330 ~ 1e99: held exactly; the quotient to 150 digits
 
 
@@ -93,8 +113,8 @@ def _length(v):
 
 
 def _check_metric(metric):
-    if metric not in METRICS + RANK_METRICS:
-        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(METRICS + RANK_METRICS)))
+    if metric not in ALL_METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(ALL_METRICS)))
 
 
 def _check_rank_bins(nbins):
@@ -108,10 +128,18 @@ def moments(vectors, device=0):
     `vectors`: any mix of Engine objects (synced; their table is used in place, never copied), torch int64/uint64 tensors on that
     device, and host uint64 numpy arrays (uploaded for the call, freed after it).  ValueError if the lengths differ; KdbHipError
     without a device."""
+    ptrs, nbins, keep = _device_pointers(vectors, device, "moments")
+    s, G, _ = gram(ptrs, nbins, device)
+    del keep
+    return s, G
+
+
+def _device_pointers(vectors, device, who):
+    """The vectors as moments() takes them -> (device pointers, number of bins, what keeps the memory alive until the kdb_ call is over)."""
     _require_device(device)
     vectors = list(vectors)
     if not vectors:
-        raise ValueError("moments needs at least one vector")
+        raise ValueError("{0} needs at least one vector".format(who))
     keep, ptrs, lengths = [], [], []
     for v in vectors:
         p, nb, owner = _device_vector(v, device)
@@ -122,10 +150,8 @@ def moments(vectors, device=0):
         raise ValueError("the vectors differ in length: {0}".format(sorted(set(lengths))))
     if any(o is not None for o in keep):
         import torch
-        torch.cuda.synchronize(int(device))              # (uploads and whatever produced the tensors: kdb_gram runs on a stream of its own)
-    s, G, _ = gram(ptrs, lengths[0], device)
-    del keep
-    return s, G
+        torch.cuda.synchronize(int(device))              # (uploads and whatever produced the tensors: the kdb_ calls run on a stream of their own)
+    return ptrs, lengths[0], keep
 
 
 def _ratio(num, den2):
@@ -171,6 +197,125 @@ def from_moments(sums, gram, nbins, metric):
     return out
 
 
+def pairstats_raw(pointers, nbins, device=0):
+    """kdb_pairstats on raw device pointers -> (stats, kernel_ms); stats: a dict of Python ints -- "S" and "nnz" per vector, "L1", "Linf",
+    "ne" and "both" as n x n lists with both triangles filled."""
+    n = len(pointers)
+    m = max(n, 1)
+    arr = (ctypes.c_void_p * m)(*[ctypes.c_void_p(int(p)) for p in pointers])
+    sums, nnz, l1 = (ctypes.c_uint64 * (2 * m))(), (ctypes.c_uint64 * m)(), (ctypes.c_uint64 * (2 * m * m))()
+    linf, ne, both = (ctypes.c_uint64 * (m * m))(), (ctypes.c_uint64 * (m * m))(), (ctypes.c_uint64 * (m * m))()
+    ms = ctypes.c_double(0)
+    _abi.check(_abi.lib().kdb_pairstats(int(device), arr, n, int(nbins), sums, nnz, l1, linf, ne, both, ctypes.byref(ms)))
+    square = lambda a: [[int(a[i * n + j]) for j in range(n)] for i in range(n)]
+    return {"S": [sums[2 * i] | (sums[2 * i + 1] << 64) for i in range(n)], "nnz": [int(nnz[i]) for i in range(n)],
+            "L1": [[l1[2 * (i * n + j)] | (l1[2 * (i * n + j) + 1] << 64) for j in range(n)] for i in range(n)],
+            "Linf": square(linf), "ne": square(ne), "both": square(both)}, ms.value
+
+
+def pairfloat_raw(pointers, nbins, device=0):
+    """kdb_pairfloat on raw device pointers -> (C, D, kernel_ms): two n x n float64 arrays (canberra; twice the squared Jensen-Shannon distance)."""
+    n = len(pointers)
+    m = max(n, 1)
+    arr = (ctypes.c_void_p * m)(*[ctypes.c_void_p(int(p)) for p in pointers])
+    c, d = np.zeros((m, m), dtype=np.float64), np.zeros((m, m), dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    ms = ctypes.c_double(0)
+    _abi.check(_abi.lib().kdb_pairfloat(int(device), arr, n, int(nbins), c.ctypes.data_as(dp), d.ctypes.data_as(dp), ctypes.byref(ms)))
+    return c[:n, :n], d[:n, :n], ms.value
+
+
+def pairstats(vectors, device=0):
+    """-> the exact per-vector and per-pair integers of kdb_pairstats as Python ints (see pairstats_raw), computed on the device.
+    `vectors` as moments() takes them: engines in place, torch tensors, host arrays; ValueError if the lengths differ."""
+    ptrs, nbins, keep = _device_pointers(vectors, device, "pairstats")
+    stats, _ = pairstats_raw(ptrs, nbins, device)
+    del keep
+    return stats
+
+
+def pairfloat(vectors, device=0):
+    """-> (C, D) of kdb_pairfloat, n x n float64 each: canberra, and D with jensenshannon = sqrt(D / 2).  `vectors` as moments() takes them."""
+    ptrs, nbins, keep = _device_pointers(vectors, device, "pairfloat")
+    c, d, _ = pairfloat_raw(ptrs, nbins, device)
+    del keep
+    return c, d
+
+
+def _quotient(num, den):
+    """num / den of two integers as the nearest float64 (fractions.Fraction rounds correctly); nan where den == 0"""
+    return float("nan") if den == 0 else float(fractions.Fraction(num, den))
+
+
+def from_pairstats(stats, nbins, metric):
+    """The n x n float64 matrix of a SWEEP_METRICS metric from kdb_pairstats' exact integers (pure host code).  With N = nbins,
+    ctt = both, ctf = nnz[i] - both, cft = nnz[j] - both, cff = N - nnz[i] - nnz[j] + both and R = ctf + cft:
+
+        cityblock    L1                           chebyshev    Linf
+        braycurtis   L1 / (S[i] + S[j])           hamming, matching   ne / N
+        jaccard      R / (ctt + R)                dice         R / (2 ctt + R)
+        rogerstanimoto, sokalmichener   2 R / (ctt + cff + 2 R)
+        russellrao   (N - ctt) / N                sokalsneath  2 R / (ctt + 2 R)
+        yule         2 ctf cft / (ctt cff + ctf cft)
+        kulsinski    (R - ctt + N) / (R + N)
+
+    The diagonal is 0.0.  A zero denominator gives nan, except where scipy returns a number for the degenerate case: jaccard of two empty
+    presence sets and yule with ctf cft == 0 (identical, nested or empty sets) are 0.0.  The quotients are formed in fractions: each value
+    is the float64 nearest the true one."""
+    if metric not in SWEEP_METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(SWEEP_METRICS)))
+    S, nnz = stats["S"], stats["nnz"]
+    n = len(S)
+    N = int(nbins)
+    out = np.empty((n, n), dtype=np.float64)
+    for i in range(n):
+        out[i][i] = SWEEP_IDENTITY[metric]
+        for j in range(i + 1, n):
+            ctt = int(stats["both"][i][j])
+            ctf, cft = int(nnz[i]) - ctt, int(nnz[j]) - ctt
+            cff, R = N - int(nnz[i]) - int(nnz[j]) + ctt, ctf + cft
+            if metric == "cityblock":
+                v = float(int(stats["L1"][i][j]))
+            elif metric == "chebyshev":
+                v = float(int(stats["Linf"][i][j]))
+            elif metric == "braycurtis":
+                v = _quotient(int(stats["L1"][i][j]), int(S[i]) + int(S[j]))
+            elif metric in ("hamming", "matching"):
+                v = _quotient(int(stats["ne"][i][j]), N)
+            elif metric == "jaccard":
+                v = 0.0 if ctt + R == 0 else _quotient(R, ctt + R)
+            elif metric == "dice":
+                v = _quotient(R, 2 * ctt + R)
+            elif metric in ("rogerstanimoto", "sokalmichener"):
+                v = _quotient(2 * R, ctt + cff + 2 * R)
+            elif metric == "russellrao":
+                v = _quotient(N - ctt, N)
+            elif metric == "sokalsneath":
+                v = _quotient(2 * R, ctt + 2 * R)
+            elif metric == "yule":
+                v = 0.0 if ctf * cft == 0 else _quotient(2 * ctf * cft, ctt * cff + ctf * cft)
+            else:                                                                    # kulsinski
+                v = _quotient(R - ctt + N, R + N)
+            out[i][j] = out[j][i] = v
+    return out
+
+
+def from_pairfloat(c, d, metric):
+    """The matrix of a FLOAT_METRICS metric from kdb_pairfloat's sums: canberra = C; jensenshannon = sqrt(D / 2), nan with an all-zero vector."""
+    if metric not in FLOAT_METRICS:
+        raise ValueError("unsupported metric '{0}': one of {1}".format(metric, ", ".join(FLOAT_METRICS)))
+    out = np.array(c if metric == "canberra" else np.sqrt(np.asarray(d, dtype=np.float64) / 2.0), dtype=np.float64)
+    np.fill_diagonal(out, SWEEP_IDENTITY[metric])
+    return out
+
+
+def _sweep_matrix(vectors, metric, device):
+    """distance_matrix for SWEEP_METRICS and FLOAT_METRICS"""
+    if metric in FLOAT_METRICS:
+        return from_pairfloat(*pairfloat(vectors, device=device), metric=metric)
+    return from_pairstats(pairstats(vectors, device=device), _length(vectors[0]), metric)
+
+
 def rank_vectors(vectors, device=0):
     """The doubled mid-ranks of every vector, as device tensors (spectrum.ranks).  An engine's table and a caller's tensor are left as
     they are and a host array is uploaded, so n rank vectors are needed: MemoryError, before any device work, if they do not fit the
@@ -195,9 +340,14 @@ def rank_vectors(vectors, device=0):
 
 def distance_matrix(vectors, metric="correlation", device=0):
     """moments() on the device, then from_moments(); for `spearman` the device ranks the vectors first (rank_vectors) and the moments are
-    those of the ranks."""
+    those of the ranks; for SWEEP_METRICS pairstats() and from_pairstats(); for FLOAT_METRICS pairfloat()."""
     _check_metric(metric)
+    metric = ALIAS_METRICS.get(metric, metric)
     vectors = list(vectors)
+    if metric in SWEEP_METRICS + FLOAT_METRICS:
+        if not vectors:
+            raise ValueError("distance_matrix needs at least one vector")
+        return _sweep_matrix(vectors, metric, device)
     if metric in RANK_METRICS:
         vectors, metric = rank_vectors(vectors, device=device), "pearson"
     s, G = moments(vectors, device=device)
@@ -272,13 +422,14 @@ def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None
 def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not_canonicalize=False, device=0):
     """Count the files of a samplesheet and compare their profiles without leaving HBM: one engine counts each file, its vector is copied
     device-to-device into row i of one n x 4^k tensor, the engine is reset; then one moments() call (for `spearman` the rows are ranked in
-    place first: no further memory).  MemoryError before counting if
+    place first: no further memory; the sweeps of SWEEP_METRICS and FLOAT_METRICS read the rows where they lie: none either).  MemoryError before counting if
     n * 8 * 4^k plus one engine does not fit the free device memory.  -> (matrix, columns, per-file metadata)."""
     from . import parse
     from .engine import Engine, KDB_N_DROP, KDB_N_EXPAND
     if type(k) is not int:
         raise TypeError("k must be an int")
     _check_metric(metric)
+    metric = ALIAS_METRICS.get(metric, metric)
     if metric in RANK_METRICS:
         _check_rank_bins(4 ** k)
     files = list(files)
@@ -305,5 +456,7 @@ def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not
         for i in range(n):
             spectrum.ranks(rows[i], out=rows[i], device=device)
         metric = "pearson"
+    if metric in SWEEP_METRICS + FLOAT_METRICS:
+        return _sweep_matrix([rows[i] for i in range(n)], metric, device), column_names_for(files), metadata
     s, G = moments([rows[i] for i in range(n)], device=device)
     return from_moments(s, G, N, metric), column_names_for(files), metadata

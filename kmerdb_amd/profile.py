@@ -210,7 +210,8 @@ def main(argv=None):
     gp.add_argument("input", nargs="+")
     gp.add_argument("kdbg")
     dp = sub.add_parser("distance", help="distance matrix of two or more .kdb count profiles (__init__.py:577-813)")
-    dp.add_argument("metric", choices=["pearson", "spearman", "correlation", "cosine", "sqeuclidean", "euclidean"])
+    from .distance import ALL_METRICS
+    dp.add_argument("metric", choices=list(ALL_METRICS))
     dp.add_argument("--column-names", default=None, help="a file with one column name per line (default: the inputs' basenames)")
     dp.add_argument("--output-delimiter", default="\t")
     dp.add_argument("--device", type=int, default=0)
