@@ -236,6 +236,33 @@ int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t n
                   double *kernel_ms_out /* may be NULL */);
 
 /*
+ * Median-of-ratios size factors of the same n vectors (Anders & Huber 2010; DESeq2's estimateSizeFactors), csrc/kdb_sizefactors.hip.h:
+ *   a bin b is eligible iff x_j[b] > 0 for every j;     L[b] = (1/n) Sum_j ln x_j[b] on eligible bins (j in order, float64)
+ *   log_sf_out[j] = median over the eligible bins of ln x_j[b] - L[b]: the middle element, or the arithmetic mean of the two middle
+ *   elements of an even number (R's and numpy's median);     *eligible_out = the number of eligible bins, exact.
+ * The size factor is exp(log_sf_out[j]), left to the caller.  With no eligible bin the call returns KDB_OK, *eligible_out = 0 and nan in
+ * log_sf_out.  The median is found by a radix select over keys recomputed from the vectors in every pass, never stored; all accumulation
+ * across the device is integer, so two calls on the same vectors return the same bits, whatever the grid.  KDB_ERR_STATE if the passes
+ * disagree (a vector changed during the call).  d_vectors, conventions and refusals as for the moments above; KDB_ERR_ARG also for a NULL
+ * log_sf_out or eligible_out; KDB_ERR_NOMEM if the float64 scratch of nbins entries does not fit.  kernel_ms_out (may be NULL): device
+ * time of the sweep and the select passes.
+ * KDB_SIZEFACTORS_WG_BINS: bins one workgroup of these kernels covers per grid stride.
+ */
+#define KDB_SIZEFACTORS_WG_BINS 512
+int kdb_size_factors(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
+                     double *log_sf_out /* n */, uint64_t *eligible_out, double *kernel_ms_out /* may be NULL */);
+
+/*
+ * One vector divided by its size factor: d_out[b] = x[b] / size_factor in IEEE float64 (x converted round-to-nearest-even), rounded half
+ * to even to an integer and stored as uint64 (as_float64 == 0: numpy's rint), or stored unrounded as float64 (as_float64 != 0).
+ * d_out: nbins 8-byte entries on the same device, 16-byte aligned; it may be d_vector itself.  KDB_ERR_ARG: a NULL or misaligned pointer,
+ * nbins == 0 or above 2^36, a size_factor that is not finite and > 0, or (integer output) a rounded quotient of 2^63 or more -- d_out is
+ * then left as it was.  kernel_ms_out (may be NULL): device time.
+ */
+int kdb_scale_counts(int device_id, const void *d_vector, uint64_t nbins, double size_factor,
+                     void *d_out /* may equal d_vector */, int as_float64, double *kernel_ms_out /* may be NULL */);
+
+/*
  * The abundance spectrum of one finished count vector -- how many bins hold each count value -- in one sweep on the device
  * (csrc/kdb_spectrum.hip.h): the reference's util.get_histo (kmerdb/util.py:92-116), and what a rank transform starts from.
  *   dense_out[v]     = number of bins that hold v, for v < KDB_SPECTRUM_DENSE; exact uint64 (at k = 17 the entry of 0 passes 2^32)

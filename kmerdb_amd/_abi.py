@@ -20,6 +20,7 @@ KDB_N_KERNELS = 8
 KDB_GRAM_MAX, KDB_GRAM_BLOCK, KDB_GRAM_WG_BINS = 64, 4, 512
 KDB_SPECTRUM_DENSE, KDB_SPECTRUM_WG_BINS = 65536, 1024
 KDB_PAIRSTATS_BLOCK, KDB_PAIRSTATS_HALF, KDB_PAIRSTATS_WG_BINS = 4, 2, 512
+KDB_SIZEFACTORS_WG_BINS = 512
 ABI_VERSION = 6
 
 # every symbol include/kdbhip.h declares: (name, restype, argtypes)
@@ -51,6 +52,9 @@ SYMBOLS = (
                                      ctypes.POINTER(ctypes.c_double)]),
     ("kdb_pairfloat", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double),
                                      ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_size_factors", ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_double), _u64p,
+                                        ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_scale_counts", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, ctypes.c_double, _vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]),
     ("kdb_spectrum", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, _u64p, _u64p, ctypes.c_uint64, _u64p, ctypes.POINTER(ctypes.c_double)]),
     ("kdb_rank_transform", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_uint64, _vp, ctypes.POINTER(ctypes.c_double)]),
     ("kdb_strand_merge", ctypes.c_int, [ctypes.c_int, _vp, _vp, ctypes.c_int]),

@@ -25,6 +25,7 @@
 #include "kdb_probe.hip.h"
 #include "kdb_gram.hip.h"
 #include "kdb_pairstats.hip.h"
+#include "kdb_sizefactors.hip.h"
 #include "kdb_spectrum.hip.h"
 #include "kdb_spectrum_host.cpp.h"
 #include "kdb_strands.hip.h"
@@ -1494,6 +1495,148 @@ int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t n
         const bool empty = isums[2 * i] == 0 || isums[2 * j] == 0;
         canberra_out[i * n + j] = canberra_out[j * n + i] = res[(size_t)r * FW];
         js_out[i * n + j] = js_out[j * n + i] = empty ? (double)NAN : res[(size_t)r * FW + 1];
+    }
+    return KDB_OK;
+}
+
+// ---- median-of-ratios size factors and normalised counts (kdb_sizefactors.hip.h, kdb_select_host.cpp.h) ----
+namespace {
+struct SizeFactorScratch {
+    const unsigned long long **vecs = nullptr; double *L = nullptr; unsigned long long *eligible = nullptr, *hist = nullptr; void *targets = nullptr;
+    uint32_t *flag = nullptr;
+    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
+    ~SizeFactorScratch()
+    {
+        (void)hipFree(vecs); (void)hipFree(L); (void)hipFree(eligible); (void)hipFree(hist); (void)hipFree(targets); (void)hipFree(flag);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+
+uint32_t sizefactor_grid(uint64_t nbins)
+{
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nbins + kdbsf::WG_BINS - 1) / kdbsf::WG_BINS, kdbsf::MAX_GRID));
+}
+}  // namespace
+
+int kdb_size_factors(int device_id, const void *const *d_vectors, int n, uint64_t nbins, double *log_sf_out, uint64_t *eligible_out, double *kernel_ms_out)
+{
+    constexpr int NB = kdbsf::NBUCKET;
+    if (int rc = pair_check_args("kdb_size_factors", d_vectors, n, nbins)) return rc;
+    if (!log_sf_out || !eligible_out) return fail(KDB_ERR_ARG, "kdb_size_factors: log_sf_out and eligible_out must not be NULL");
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    DeviceGuard g(device_id);
+
+    SizeFactorScratch sc;
+    std::vector<const unsigned long long *> ptrs((size_t)n);
+    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
+    const size_t hist_bytes = (size_t)n * 2 * NB * sizeof(uint64_t);
+    if (hipMalloc((void **)&sc.L, ((nbins + 1) & ~1ull) * sizeof(double)) != hipSuccess || hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess ||
+        hipMalloc((void **)&sc.eligible, sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&sc.hist, hist_bytes) != hipSuccess ||
+        hipMalloc(&sc.targets, (size_t)n * sizeof(kdbsf::Target)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_size_factors: no room for the float64 scratch of %llu bins", (unsigned long long)nbins);
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&sc.a));
+    HIP_TRY(hipEventCreate(&sc.b));
+    const uint32_t gx = sizefactor_grid(nbins);                                        // (any grid gives the same integers)
+    double total_ms = 0.0;
+    auto add_elapsed = [&]() -> hipError_t {
+        float ms = 0;
+        const hipError_t e = hipEventElapsedTime(&ms, sc.a, sc.b);
+        total_ms += (double)ms;
+        return e;
+    };
+
+    uint64_t m = 0;
+    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemsetAsync(sc.eligible, 0, sizeof(uint64_t), sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    hipLaunchKernelGGL(kdbsf::geomean_kernel, dim3(gx), dim3(kdbsf::TPB), 0, sc.st, sc.vecs, n, nbins, sc.L, sc.eligible);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    HIP_TRY(hipMemcpyAsync(&m, sc.eligible, sizeof(uint64_t), hipMemcpyDeviceToHost, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    HIP_TRY(add_elapsed());
+    *eligible_out = m;
+    if (kernel_ms_out) *kernel_ms_out = total_ms;
+    if (m == 0) {
+        for (int j = 0; j < n; j++) log_sf_out[j] = (double)NAN;
+        return KDB_OK;
+    }
+
+    std::vector<kdbselect::Select> sel((size_t)n);
+    uint64_t lo, hi;
+    kdbselect::median_ranks(m, &lo, &hi);
+    for (auto &s : sel) s.start(lo, hi);
+    std::vector<kdbsf::Target> targets((size_t)n);
+    std::vector<uint64_t> hist((size_t)n * 2 * NB);
+    for (int pass = 0; pass < kdbselect::NPASS; pass++) {
+        for (int j = 0; j < n; j++) targets[j] = kdbsf::Target{{sel[j].prefix[0], sel[j].prefix[1]}, (uint32_t)sel[j].ntargets, 0};
+        HIP_TRY(hipMemcpyAsync(sc.targets, targets.data(), targets.size() * sizeof(kdbsf::Target), hipMemcpyHostToDevice, sc.st));
+        HIP_TRY(hipMemsetAsync(sc.hist, 0, hist_bytes, sc.st));
+        HIP_TRY(hipEventRecord(sc.a, sc.st));
+        hipLaunchKernelGGL(kdbsf::select_kernel, dim3(gx, (uint32_t)n), dim3(kdbsf::TPB), 0, sc.st, sc.vecs, (const double *)sc.L, nbins,
+                           (const kdbsf::Target *)sc.targets, kdbselect::pass_shift(pass), kdbselect::pass_width(pass), sc.hist);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(sc.b, sc.st));
+        HIP_TRY(hipMemcpyAsync(hist.data(), sc.hist, hist_bytes, hipMemcpyDeviceToHost, sc.st));
+        HIP_TRY(hipStreamSynchronize(sc.st));
+        HIP_TRY(add_elapsed());
+        for (int j = 0; j < n; j++)
+            if (!sel[j].step(&hist[(size_t)j * 2 * NB], &hist[(size_t)j * 2 * NB + NB], pass))
+                return fail(KDB_ERR_STATE, "kdb_size_factors: pass %d of the select found no element of the wanted rank in vector %d: the vectors changed during the call", pass, j);
+    }
+    for (int j = 0; j < n; j++) log_sf_out[j] = kdbselect::median_of(sel[j].low(), sel[j].high());
+    if (kernel_ms_out) *kernel_ms_out = total_ms;
+    return KDB_OK;
+}
+
+int kdb_scale_counts(int device_id, const void *d_vector, uint64_t nbins, double size_factor, void *d_out, int as_float64, double *kernel_ms_out)
+{
+    if (!d_vector || !d_out) return fail(KDB_ERR_ARG, "kdb_scale_counts: a vector is NULL");
+    if ((((uintptr_t)d_vector | (uintptr_t)d_out) & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_scale_counts: a vector is not 16-byte aligned");
+    if (nbins == 0 || nbins > kdbsf::NBINS_MAX) return fail(KDB_ERR_ARG, "kdb_scale_counts: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)");
+    if (!(size_factor > 0.0) || !std::isfinite(size_factor)) return fail(KDB_ERR_ARG, "kdb_scale_counts: the size factor %g is not finite and positive", size_factor);
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    DeviceGuard g(device_id);
+
+    SizeFactorScratch sc;
+    if (hipMalloc((void **)&sc.flag, sizeof(uint32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_scale_counts: no room for the flag word");
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&sc.a));
+    HIP_TRY(hipEventCreate(&sc.b));
+    const uint32_t gx = sizefactor_grid(nbins);
+    const unsigned long long *x = (const unsigned long long *)d_vector;
+    uint32_t flag = 0;
+    HIP_TRY(hipMemsetAsync(sc.flag, 0, sizeof(uint32_t), sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    // x < 2^64 rounds to at most 2^64: only a size factor of 2 or less can bring a quotient to 2^63.  Then a first sweep looks and writes
+    // nothing, so that a refused call leaves d_out (which may be the input) as it was.
+    if (!as_float64 && size_factor <= 2.0) {
+        hipLaunchKernelGGL(kdbsf::scale_kernel, dim3(gx), dim3(kdbsf::TPB), 0, sc.st, x, nbins, size_factor, d_out, 0, 0, sc.flag);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(&flag, sc.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, sc.st));
+        HIP_TRY(hipStreamSynchronize(sc.st));
+        if (flag != 0) return fail(KDB_ERR_ARG, "kdb_scale_counts: a count divided by the size factor %g reaches 2^63: it has no place in an int64 matrix", size_factor);
+    }
+    hipLaunchKernelGGL(kdbsf::scale_kernel, dim3(gx), dim3(kdbsf::TPB), 0, sc.st, x, nbins, size_factor, d_out, as_float64 ? 1 : 0, 1, sc.flag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    if (kernel_ms_out) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
+        *kernel_ms_out = (double)ms;
     }
     return KDB_OK;
 }

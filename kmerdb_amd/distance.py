@@ -338,12 +338,25 @@ def rank_vectors(vectors, device=0):
     return [spectrum.ranks(v, device=device) for v in vectors]
 
 
-def distance_matrix(vectors, metric="correlation", device=0):
+def _check_normalize(normalize):
+    from . import matrix
+    matrix.check_normalize(normalize)
+
+
+def distance_matrix(vectors, metric="correlation", device=0, normalize=None):
     """moments() on the device, then from_moments(); for `spearman` the device ranks the vectors first (rank_vectors) and the moments are
-    those of the ranks; for SWEEP_METRICS pairstats() and from_pairstats(); for FLOAT_METRICS pairfloat()."""
+    those of the ranks; for SWEEP_METRICS pairstats() and from_pairstats(); for FLOAT_METRICS pairfloat().  normalize="DESeq2": the
+    vectors are first divided by their median-of-ratios size factors and rounded to integers (matrix.normalize: new vectors for engines and
+    the caller's tensors, which stay as they are), and everything above runs on those."""
     _check_metric(metric)
+    _check_normalize(normalize)
     metric = ALIAS_METRICS.get(metric, metric)
     vectors = list(vectors)
+    if normalize is not None:
+        if not vectors:
+            raise ValueError("distance_matrix needs at least one vector")
+        from . import matrix
+        vectors, _ = matrix.normalize(vectors, device=device, ints=True)
     if metric in SWEEP_METRICS + FLOAT_METRICS:
         if not vectors:
             raise ValueError("distance_matrix needs at least one vector")
@@ -398,12 +411,14 @@ def column_names_for(inputs, column_names=None):
     return columns
 
 
-def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None, device=0):
+def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None, device=0, normalize=None):
     """The reference driver for two or more .kdb files (kmerdb/__init__.py:616-661, :796-813): read the profiles, one sweep on the device,
-    print the matrix.  -> the matrix."""
+    print the matrix.  normalize="DESeq2": the profiles are normalised where they were uploaded (`kmerdb matrix DESeq2`) first.
+    -> the matrix."""
     from . import fileutil
     inputs = list(inputs)
     _check_metric(metric)
+    _check_normalize(normalize)
     if len(inputs) < 2:
         raise ValueError("'kmerdb distance' requires more than one .kdb file as positional inputs")
     if not all(os.path.splitext(p)[-1] == ".kdb" for p in inputs):
@@ -414,21 +429,23 @@ def distances(inputs, metric, column_names=None, output_delimiter="\t", out=None
     columns = column_names_for(inputs, column_names)
     _require_device(device)
     profiles = [fileutil.read_kdb(p).counts for p in inputs]
-    dist = distance_matrix(profiles, metric=metric, device=device)
+    dist = distance_matrix(profiles, metric=metric, device=device, normalize=normalize)     # (host arrays: scaled where they are uploaded)
     (sys.stdout if out is None else out).write(format_matrix(dist, columns, output_delimiter))
     return dist
 
 
-def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not_canonicalize=False, device=0):
+def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not_canonicalize=False, device=0, normalize=None):
     """Count the files of a samplesheet and compare their profiles without leaving HBM: one engine counts each file, its vector is copied
     device-to-device into row i of one n x 4^k tensor, the engine is reset; then one moments() call (for `spearman` the rows are ranked in
     place first: no further memory; the sweeps of SWEEP_METRICS and FLOAT_METRICS read the rows where they lie: none either).  MemoryError before counting if
-    n * 8 * 4^k plus one engine does not fit the free device memory.  -> (matrix, columns, per-file metadata)."""
+    n * 8 * 4^k plus one engine does not fit the free device memory.  normalize="DESeq2": the rows are divided by their size factors
+    and rounded, in place, before anything else (matrix.normalize).  -> (matrix, columns, per-file metadata)."""
     from . import parse
     from .engine import Engine, KDB_N_DROP, KDB_N_EXPAND
     if type(k) is not int:
         raise TypeError("k must be an int")
     _check_metric(metric)
+    _check_normalize(normalize)
     metric = ALIAS_METRICS.get(metric, metric)
     if metric in RANK_METRICS:
         _check_rank_bins(4 ** k)
@@ -451,7 +468,10 @@ def profile_distances(files, k, metric="correlation", no_ambiguous=False, do_not
             rows[i].copy_(eng.table_tensor())
             torch.cuda.synchronize(int(device))
             eng.reset()
-    if metric in RANK_METRICS:                                               # the rows are this function's own: ranked where they lie
+    if normalize is not None:                                                # the rows are this function's own: scaled where they lie
+        from . import matrix
+        matrix.normalize([rows[i] for i in range(n)], device=device, ints=True, inplace=True)
+    if metric in RANK_METRICS:                                               # ranked where they lie, too
         from . import spectrum
         for i in range(n):
             spectrum.ranks(rows[i], out=rows[i], device=device)

@@ -187,7 +187,7 @@ def profile(inputs, k, output_name, no_ambiguous=False, do_not_canonicalize=Fals
 
 def main(argv=None):
     """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
-    `graph`, `distance <metric> a.kdb b.kdb ...` and `spectrum a.kdb ...` beside it."""
+    `graph`, `distance <metric> a.kdb b.kdb ...`, `matrix <method> a.kdb b.kdb ...` and `spectrum a.kdb ...` beside it."""
     import argparse
     ap = argparse.ArgumentParser(prog="kmerdb_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -214,8 +214,17 @@ def main(argv=None):
     dp.add_argument("metric", choices=list(ALL_METRICS))
     dp.add_argument("--column-names", default=None, help="a file with one column name per line (default: the inputs' basenames)")
     dp.add_argument("--output-delimiter", default="\t")
+    dp.add_argument("--normalize", choices=["DESeq2"], default=None, help="divide every profile by its median-of-ratios size factor first")
     dp.add_argument("--device", type=int, default=0)
     dp.add_argument("input", nargs="+")
+    mp = sub.add_parser("matrix", help="the count matrix of two or more .kdb profiles, as it is or normalised (__init__.py:815-1043)")
+    mp.add_argument("method", choices=["from", "Frequency", "DESeq2"])
+    mp.add_argument("--no-normalized-ints", action="store_true", help="DESeq2: print the float64 quotients, not the rounded integers")
+    mp.add_argument("--with-index", action="store_true", help="print the row index as a first column")
+    mp.add_argument("--column-names", default=None, help="a file with one column name per line (default: the inputs' basenames)")
+    mp.add_argument("--output-delimiter", default="\t")
+    mp.add_argument("--device", type=int, default=0)
+    mp.add_argument("input", nargs="+")
     sp = sub.add_parser("spectrum", help="abundance spectrum of .kdb count profiles: `count<TAB>bins` rows, the counts that occur, ascending")
     sp.add_argument("--device", type=int, default=0)
     sp.add_argument("input", nargs="+")
@@ -230,7 +239,13 @@ def main(argv=None):
         return 0
     if a.cmd == "distance":
         from . import distance
-        distance.distances(a.input, a.metric, column_names=a.column_names, output_delimiter=a.output_delimiter, device=a.device)
+        extra = {} if a.normalize is None else {"normalize": a.normalize}              # (without the flag the call is what it always was)
+        distance.distances(a.input, a.metric, column_names=a.column_names, output_delimiter=a.output_delimiter, device=a.device, **extra)
+        return 0
+    if a.cmd == "matrix":
+        from . import matrix
+        matrix.matrix(a.input, a.method, column_names=a.column_names, output_delimiter=a.output_delimiter, with_index=a.with_index,
+                      no_normalized_ints=a.no_normalized_ints, device=a.device)
         return 0
     if a.cmd == "graph":
         from . import graph
