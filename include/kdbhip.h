@@ -184,10 +184,17 @@ int kdb_strand_merge(int device_id, void *d_fwd, void *d_table, int k);
  * nbins == 0 (or above 2^36: no device holds such a vector), a NULL or misaligned pointer, or some S[i] >= 2^64 (the sums are exact always; the products may have wrapped).
  * KDB_ERR_NOMEM: the scratch does not fit.  kernel_ms_out (may be NULL): device time of the sweep, by HIP events.
  * KDB_GRAM_BLOCK / KDB_GRAM_WG_BINS: the kernel's constants -- vectors per register block, bins one workgroup covers per grid stride.
+ * KDB_GRAM_GRID_MAX / _MAX_MANY_ROWS / _MANY_ROWS: the most workgroups per row (a row: one pair of blocks here, a block against up to
+ * KDB_PAIRSTATS_HALF vectors in kdb_pairstats, which shares the three) that sweep the whole chunks -- the first cap for a call of fewer
+ * than KDB_GRAM_GRID_MANY_ROWS rows, the second from that many rows on.  A workgroup past its first KDB_GRAM_WG_BINS bins strides on by
+ * grid x KDB_GRAM_WG_BINS.  Any grid gives the same integers; the tests take their shapes from these.
  */
 #define KDB_GRAM_MAX 64
 #define KDB_GRAM_BLOCK 4
 #define KDB_GRAM_WG_BINS 512
+#define KDB_GRAM_GRID_MAX 1024
+#define KDB_GRAM_GRID_MAX_MANY_ROWS 256
+#define KDB_GRAM_GRID_MANY_ROWS 4
 int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
              uint64_t *sums_out   /* 2*n   words: lo, hi of S[i]            */,
              uint64_t *gram_out   /* 2*n*n words: lo, hi of G[i][j], both triangles filled */,
@@ -210,7 +217,7 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
  * nbins == 0 or above 2^36, a NULL or misaligned pointer, a NULL output, or some S[i] >= 2^64.  KDB_ERR_NOMEM: the scratch does not fit.
  * kernel_ms_out (may be NULL): device time of the sweep, by HIP events.
  * KDB_PAIRSTATS_BLOCK / _HALF / _WG_BINS: the kernel's constants -- vectors per register block, vectors of the second block a row takes
- * off the diagonal, bins one workgroup covers per grid stride.
+ * off the diagonal, bins one workgroup covers per grid stride.  The grid's caps are kdb_gram's (KDB_GRAM_GRID_*), by this call's rows.
  */
 #define KDB_PAIRSTATS_BLOCK 4
 #define KDB_PAIRSTATS_HALF 2
@@ -230,7 +237,9 @@ int kdb_pairstats(int device_id, const void *const *d_vectors, int n, uint64_t n
  * term is non-negative and is formed before it is added; no atomics; the grid depends on nbins alone and the order of the additions is
  * fixed: two calls on the same vectors return the same bits (on one build; not promised across builds).  IEEE division: the library is
  * built without fast-math.  Conventions and refusals as above.  kernel_ms_out (may be NULL): device time of the float sweep alone.
+ * KDB_PAIRFLOAT_GRID_MAX: the most workgroups per pair that sweep the whole chunks (KDB_PAIRSTATS_WG_BINS bins each per grid stride).
  */
+#define KDB_PAIRFLOAT_GRID_MAX 512
 int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
                   double *canberra_out /* n*n */, double *js_out /* n*n */,
                   double *kernel_ms_out /* may be NULL */);
@@ -246,9 +255,11 @@ int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t n
  * disagree (a vector changed during the call).  d_vectors, conventions and refusals as for the moments above; KDB_ERR_ARG also for a NULL
  * log_sf_out or eligible_out; KDB_ERR_NOMEM if the float64 scratch of nbins entries does not fit.  kernel_ms_out (may be NULL): device
  * time of the sweep and the select passes.
- * KDB_SIZEFACTORS_WG_BINS: bins one workgroup of these kernels covers per grid stride.
+ * KDB_SIZEFACTORS_WG_BINS: bins one workgroup of these kernels covers per grid stride.  KDB_SIZEFACTORS_GRID_MAX: the most workgroups
+ * (per sample) of a sweep, of kdb_scale_counts' too.
  */
 #define KDB_SIZEFACTORS_WG_BINS 512
+#define KDB_SIZEFACTORS_GRID_MAX 1024
 int kdb_size_factors(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
                      double *log_sf_out /* n */, uint64_t *eligible_out, double *kernel_ms_out /* may be NULL */);
 

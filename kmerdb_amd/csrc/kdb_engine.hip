@@ -704,6 +704,9 @@ namespace {
 
 struct GramGroup { uint32_t row0, nrows; int na, nb; bool diag; };
 
+// the most workgroups per row of kdb_gram's and kdb_pairstats' sweeps (include/kdbhip.h)
+uint32_t gram_grid_max(uint32_t nrows) { return nrows < KDB_GRAM_GRID_MANY_ROWS ? (uint32_t)KDB_GRAM_GRID_MAX : (uint32_t)KDB_GRAM_GRID_MAX_MANY_ROWS; }
+
 void gram_launch(const GramGroup &gr, uint32_t gx, const unsigned long long *const *vecs, const kdbgram::Row *rows, uint32_t nchunks, uint32_t pstride, ulonglong2 *partials,
                  hipStream_t st)
 {
@@ -1224,7 +1227,7 @@ int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins,
     const uint32_t nrows = (uint32_t)rows.size();
     // gram_kernel takes the whole chunks, gram_tail_kernel the bins behind them; a row's partials: one per workgroup, then the tail's
     const uint32_t nchunks = (uint32_t)(nbins / kdbgram::CHUNK_BINS), wg_chunks = kdbgram::TPB / 64;
-    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, nrows <= 3 ? 1024u : 256u));       // (any grid gives the same integers)
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, gram_grid_max(nrows)));       // (any grid gives the same integers)
     const uint32_t nparts = gx + 1;
     struct Scratch {
         const unsigned long long **vecs = nullptr; kdbgram::Row *rows = nullptr; ulonglong2 *partials = nullptr, *out = nullptr;
@@ -1373,7 +1376,7 @@ int kdb_pairstats(int device_id, const void *const *d_vectors, int n, uint64_t n
     const uint32_t nrows = (uint32_t)rows.size();
     // pair_kernel takes the whole chunks, pair_tail_kernel the bins behind them; a row's partials: one per workgroup, then the tail's
     const uint32_t nchunks = (uint32_t)(nbins / kdbpair::CHUNK_BINS), wg_chunks = kdbpair::TPB / 64;
-    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, nrows <= 3 ? 1024u : 256u));       // (any grid gives the same integers)
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, gram_grid_max(nrows)));       // (any grid gives the same integers)
     const uint32_t nparts = gx + 1;
     PairScratch sc;
     std::vector<const unsigned long long *> ptrs((size_t)n);
@@ -1456,7 +1459,7 @@ int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t n
     for (int i = 0; i < n; i++) for (int j = i + 1; j < n; j++) rows.push_back(kdbpair::FloatRow{(uint8_t)i, (uint8_t)j});
     const uint32_t nrows = (uint32_t)rows.size();
     const uint32_t nchunks = (uint32_t)(nbins / kdbpair::CHUNK_BINS), wg_chunks = kdbpair::TPB / 64;
-    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, 512u));          // (a function of nbins alone: the order of the additions is fixed)
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, (uint32_t)KDB_PAIRFLOAT_GRID_MAX));          // (a function of nbins alone: the order of the additions is fixed)
     const uint32_t nparts = gx + 1;
     PairScratch sc;
     std::vector<const unsigned long long *> ptrs((size_t)n);

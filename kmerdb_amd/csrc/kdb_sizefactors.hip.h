@@ -31,7 +31,7 @@ constexpr int WG_BINS = (TPB / 64) * CHUNK_BINS;   // bins one workgroup covers 
 constexpr int MAX_GRID = 1024;                     // workgroups per sample: with 2^36 bins a workgroup meets 2^26, its LDS counters hold 2^32
 constexpr uint64_t NBINS_MAX = 1ull << 36;
 constexpr int NBUCKET = kdbselect::NBUCKET;
-static_assert(WG_BINS == KDB_SIZEFACTORS_WG_BINS, "include/kdbhip.h states the kernels' constant");
+static_assert(WG_BINS == KDB_SIZEFACTORS_WG_BINS && MAX_GRID == KDB_SIZEFACTORS_GRID_MAX, "include/kdbhip.h states the kernels' constants");
 static_assert(NBINS_MAX / MAX_GRID < (1ull << 32), "a workgroup's 32-bit histogram counters and a lane's 32-bit eligible count cannot wrap");
 
 typedef unsigned long long u64;
