@@ -353,6 +353,44 @@ int kdb_window_ids(kdb_engine *e, const uint8_t *bases, size_t nbytes,
                    const uint64_t *read_offsets, size_t nreads, uint64_t *ids_out);
 
 /*
+ * Reads scored against a finished profile (csrc/kdb_score.hip.h): the reference's markov_probability, kmerdb/probability.py:36-151 --
+ * the log-probability of a sequence under the (k-1)-order Markov chain the 4^k count vector defines -- for a batch of records, one
+ * random 32-byte read of the vector per window instead of one index.read_line through a .kdbi file (probability.py:77-99).
+ * With v the vector, a = pseudocount and total' = total + a 4^k, a window w is scored iff kdb_window_ids of a forward ids-engine emits an
+ * id for it (whole inside its record, every residue ACGT), and then
+ *   c(w) = v[id(w)] + a                (canonical != 0: v[min(id, rc(id))] + a, rc as in kdb_strand_merge)
+ *   D(w) = Sum_{x in ACGT} c(prefix_{k-1}(w) x): on a forward profile the four bins 4 (id >> 2) .. + 3; at k = 1 the whole vector
+ *   the first scored window of a record contributes ln c(w) - ln total' (the reference's px, probability.py:75), every later one
+ *   ln c(w) - ln D(w) (its ast = qt / sum_qses, :91-99, :130-133); a window with c(w) == 0 contributes -inf (never nan).
+ *   log10_p_out[r]      = (the sum of the record's terms) / ln 10; nan if the record has no scored window.  FLOAT: float64 natural logs
+ *                         of integers converted once (D, up to 2^66, is formed in 128 bits and rounded to nearest even once), added in an
+ *                         order fixed by the record's length and KDB_SCORE_PIECE alone: a record's outputs do not depend on the grid, on the
+ *                         other records of the batch or on its place among them, and two calls return the same bits (on one build).
+ *   windows_out[r]      = number of scored windows                                                     EXACT
+ *   zero_windows_out[r] = number of scored windows whose bin v[...] is 0 (before the pseudocount)      EXACT
+ *   min_count_out[r]    = the smallest v[...] over the scored windows, 2^64 - 1 if there are none      EXACT
+ * d_vector: 4^k uint64 on device_id, 16-byte aligned, read only.  bases / read_offsets: host memory, as for kdb_window_ids, at most 2^30
+ * residues per call.  Synchronous; the caller has synchronised whatever produced the vector; scratch is allocated and freed inside the call.
+ * KDB_SCORE_CONTINUES: record 0 is the next piece of the previous call's last record: it starts with the last k-1 residues already given,
+ * every one of its windows is a transition (no initial term) and it is exempt from the length check, as in kdb_submit_ex; the caller adds
+ * the pieces' outputs.
+ * KDB_ERR_ARG: k outside 1..17, a NULL or misaligned pointer, total == 0, total + pseudocount 4^k or 4 pseudocount not below 2^64, offsets
+ * that do not rise from 0 to nbytes, more than 2^30 residues, unknown flags.  KDB_ERR_SHORT_READ / KDB_ERR_BAD_RESIDUE: what kdb_window_ids
+ * refuses (kmer.py:461-463; kmer.py:309 / :170), the outputs are then not written.  KDB_ERR_NOMEM: the scratch does not fit.
+ * kernel_ms_out (may be NULL): device time of the residue check and the two scoring kernels, by HIP events.
+ * KDB_SCORE_PIECE: windows one wave scores; a record of more windows is cut into pieces of that many, summed in piece order.
+ * KDB_SCORE_LANES: lanes of the wave: a lane adds at most KDB_SCORE_PIECE / KDB_SCORE_LANES terms in a row before the log2(KDB_SCORE_LANES)
+ * levels of the butterfly; every piece then adds two numbers to the record's sum.
+ */
+#define KDB_SCORE_CONTINUES 1
+#define KDB_SCORE_PIECE 2048
+#define KDB_SCORE_LANES 64
+int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, uint64_t total, uint64_t pseudocount,
+                    const uint8_t *bases, size_t nbytes, const uint64_t *read_offsets, size_t nreads, int flags,
+                    double *log10_p_out, uint64_t *windows_out, uint64_t *zero_windows_out, uint64_t *min_count_out /* nreads each */,
+                    double *kernel_ms_out /* may be NULL */);
+
+/*
  * Host-side record splitter (no GPU work): what Bio.SeqIO.parse does for kmerdb/parse.py:50-85 on this path.
  * FASTQ: parses whole records of text[0, n) into bases_out (concatenated residues) and offsets_out
  * (nreads+1 entries); *consumed_out = bytes of text used (stops before a trailing partial record unless at_eof).

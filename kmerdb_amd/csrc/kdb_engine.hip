@@ -29,6 +29,7 @@
 #include "kdb_spectrum.hip.h"
 #include "kdb_spectrum_host.cpp.h"
 #include "kdb_strands.hip.h"
+#include "kdb_score.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
 
@@ -2045,6 +2046,115 @@ int kdb_window_ids(kdb_engine *e, const uint8_t *bases, size_t nbytes, const uin
     if (c.bad_layout) return fail(KDB_ERR_ARG, "read_offsets must rise from 0 to nbytes");
     if (c.n_short) return fail(KDB_ERR_SHORT_READ, "%llu record(s) shorter than k=%d (reference: kmer.py:461-463 raises)", c.n_short, e->k);
     if (c.n_bad) return fail(KDB_ERR_BAD_RESIDUE, "%llu residue(s) outside ACGTN (reference: kmer.py:309 / :170 raises)", c.n_bad);
+    return KDB_OK;
+}
+
+// ---- reads scored against a profile (kdb_score.hip.h) ----
+namespace {
+struct ScoreScratch {
+    uint8_t *bases = nullptr; uint64_t *offs = nullptr; uint32_t *piece_rec = nullptr, *rec_piece0 = nullptr; kdbscore::PieceOut *pieces = nullptr;
+    kdb::DevCounters *ctr = nullptr; double *log10_p = nullptr; unsigned long long *ints = nullptr;
+    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
+    ~ScoreScratch()
+    {
+        (void)hipFree(bases); (void)hipFree(offs); (void)hipFree(piece_rec); (void)hipFree(rec_piece0); (void)hipFree(pieces); (void)hipFree(ctr);
+        (void)hipFree(log10_p); (void)hipFree(ints);
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
+}  // namespace
+
+int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, uint64_t total, uint64_t pseudocount, const uint8_t *bases, size_t nbytes,
+                    const uint64_t *offs, size_t nreads, int flags, double *log10_p_out, uint64_t *windows_out, uint64_t *zero_windows_out,
+                    uint64_t *min_count_out, double *kernel_ms_out)
+{
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (k < 1 || k > 17) return fail(KDB_ERR_ARG, "kdb_score_reads: k=%d out of range 1..17", k);
+    if (!d_vector || ((uintptr_t)d_vector & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_score_reads: the vector is NULL or not 16-byte aligned");
+    if (flags & ~KDB_SCORE_CONTINUES) return fail(KDB_ERR_ARG, "kdb_score_reads: unknown flags %d", flags);
+    if (total == 0) return fail(KDB_ERR_ARG, "kdb_score_reads: total is 0 (an empty profile gives no probabilities)");
+    const uint64_t nbins = 1ull << (2 * k);
+    const unsigned __int128 total2 = (unsigned __int128)total + (unsigned __int128)pseudocount * nbins;
+    if ((total2 >> 64) != 0 || pseudocount >= (1ull << 62))
+        return fail(KDB_ERR_ARG, "kdb_score_reads: total + pseudocount * 4^k and 4 * pseudocount must stay below 2^64");
+    if (nreads == 0) return nbytes == 0 ? KDB_OK : fail(KDB_ERR_ARG, "kdb_score_reads: residues but no records");
+    if (!offs || (!bases && nbytes) || !log10_p_out || !windows_out || !zero_windows_out || !min_count_out) return fail(KDB_ERR_ARG, "kdb_score_reads: NULL buffer");
+    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_score_reads: at most 2^30 residues per call");
+    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_score_reads: at most 2^30 records per call");
+    const bool continues = (flags & KDB_SCORE_CONTINUES) != 0;
+    // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
+    if (offs[0] != 0 || offs[nreads] != nbytes) return fail(KDB_ERR_ARG, "read_offsets must start at 0 and end at nbytes");
+    std::vector<uint32_t> rec_piece0(nreads + 1);
+    uint64_t npieces = 0, nshort = 0;
+    for (size_t r = 0; r < nreads; r++) {
+        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return fail(KDB_ERR_ARG, "read_offsets must rise from 0 to nbytes");
+        const uint64_t len = offs[r + 1] - offs[r];
+        if (len < (uint64_t)k && !(r == 0 && continues)) nshort++;
+        const uint64_t nwin = len >= (uint64_t)k ? len - (uint64_t)k + 1 : 0;
+        rec_piece0[r] = (uint32_t)npieces;
+        npieces += std::max<uint64_t>(1, (nwin + kdbscore::PIECE - 1) / kdbscore::PIECE);         // (< 2^31: 2^30 records and 2^30 windows at most)
+    }
+    rec_piece0[nreads] = (uint32_t)npieces;
+    if (nshort) return fail(KDB_ERR_SHORT_READ, "%llu record(s) shorter than k=%d (reference: kmer.py:461-463 raises)", (unsigned long long)nshort, k);
+    std::vector<uint32_t> piece_rec;
+    if (npieces != nreads) {
+        piece_rec.resize(npieces);
+        for (size_t r = 0; r < nreads; r++)
+            for (uint32_t p = rec_piece0[r]; p < rec_piece0[r + 1]; p++) piece_rec[p] = (uint32_t)r;
+    }
+    int ndev = 0;
+    HIP_TRY(hipGetDeviceCount(&ndev));
+    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
+    DeviceGuard g(device_id);
+
+    ScoreScratch sc;
+    if (hipMalloc((void **)&sc.bases, ((nbytes + 15) & ~(size_t)15) + 32) != hipSuccess /* (piece_kernel's aligned words reach 23 bytes past a window's start) */ || hipMalloc((void **)&sc.offs, (nreads + 1) * sizeof(uint64_t)) != hipSuccess ||
+        hipMalloc((void **)&sc.rec_piece0, (nreads + 1) * sizeof(uint32_t)) != hipSuccess ||
+        (!piece_rec.empty() && hipMalloc((void **)&sc.piece_rec, npieces * sizeof(uint32_t)) != hipSuccess) ||
+        hipMalloc((void **)&sc.pieces, npieces * sizeof(kdbscore::PieceOut)) != hipSuccess || hipMalloc((void **)&sc.ctr, sizeof(kdb::DevCounters)) != hipSuccess ||
+        hipMalloc((void **)&sc.log10_p, nreads * sizeof(double)) != hipSuccess || hipMalloc((void **)&sc.ints, 3 * nreads * sizeof(uint64_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(KDB_ERR_NOMEM, "kdb_score_reads: no room for the scratch of %zu residues in %zu records", nbytes, nreads);
+    }
+    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreate(&sc.a));
+    HIP_TRY(hipEventCreate(&sc.b));
+    kdb::DevCounters c;
+    memset(&c, 0, sizeof c);
+    c.sus_count = 1;                       // more than sus_cap = 0: resolve_suspects_kernel judges every residue of the batch itself
+    if (nbytes) HIP_TRY(hipMemcpyAsync(sc.bases, bases, nbytes, hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.rec_piece0, rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, sc.st));
+    if (!piece_rec.empty()) HIP_TRY(hipMemcpyAsync(sc.piece_rec, piece_rec.data(), npieces * sizeof(uint32_t), hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipMemcpyAsync(sc.ctr, &c, sizeof c, hipMemcpyHostToDevice, sc.st));
+    HIP_TRY(hipEventRecord(sc.a, sc.st));
+    // what kdb_window_ids refuses: bytes with bit 7 set, letters outside ACGTN that no N shields (kmer.py:309 / :170)
+    hipLaunchKernelGGL(kdb::hibit_check_kernel, dim3(1024), dim3(256), 0, sc.st, (const uint8_t *)sc.bases, (uint64_t)nbytes, sc.ctr);
+    const unsigned check_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (nbytes / 64 + 255) / 256));
+    hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(check_grid), dim3(256), 0, sc.st, (const uint8_t *)sc.bases, (uint64_t)nbytes, (const uint64_t *)sc.offs,
+                       (uint64_t)nreads, k, sc.ctr);
+    unsigned long long *ints = sc.ints;
+    hipLaunchKernelGGL(kdbscore::piece_kernel, dim3((unsigned)((npieces + kdbscore::TPB / 64 - 1) / (kdbscore::TPB / 64))), dim3(kdbscore::TPB), 0, sc.st,
+                       (const uint8_t *)sc.bases, (const uint64_t *)sc.offs, (const uint32_t *)sc.piece_rec, (const uint32_t *)sc.rec_piece0, (uint32_t)npieces,
+                       (const unsigned long long *)d_vector, k, canonical ? 1 : 0, (unsigned long long)pseudocount, sc.pieces);
+    hipLaunchKernelGGL(kdbscore::record_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, sc.st, (const kdbscore::PieceOut *)sc.pieces,
+                       (const uint32_t *)sc.rec_piece0, (uint64_t)nreads, (double)(uint64_t)total2, continues ? 1 : 0, sc.log10_p, ints, ints + nreads, ints + 2 * nreads);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(sc.b, sc.st));
+    HIP_TRY(hipMemcpyAsync(&c, sc.ctr, sizeof c, hipMemcpyDeviceToHost, sc.st));
+    HIP_TRY(hipStreamSynchronize(sc.st));
+    if (kernel_ms_out) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
+        *kernel_ms_out = (double)ms;
+    }
+    if (c.n_bad) return fail(KDB_ERR_BAD_RESIDUE, "%llu residue(s) outside ACGTN (reference: kmer.py:309 / :170 raises)", c.n_bad);
+    HIP_TRY(hipMemcpy(log10_p_out, sc.log10_p, nreads * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(windows_out, ints, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(zero_windows_out, ints + nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(min_count_out, ints + 2 * nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return KDB_OK;
 }
 

@@ -185,9 +185,8 @@ def profile(inputs, k, output_name, no_ambiguous=False, do_not_canonicalize=Fals
     return counts, metadata, out
 
 
-def main(argv=None):
-    """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
-    `graph`, `distance <metric> a.kdb b.kdb ...`, `matrix <method> a.kdb b.kdb ...` and `spectrum a.kdb ...` beside it."""
+def build_parser():
+    """the argument parser of `python -m kmerdb_amd`"""
     import argparse
     ap = argparse.ArgumentParser(prog="kmerdb_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -228,7 +227,25 @@ def main(argv=None):
     sp = sub.add_parser("spectrum", help="abundance spectrum of .kdb count profiles: `count<TAB>bins` rows, the counts that occur, ascending")
     sp.add_argument("--device", type=int, default=0)
     sp.add_argument("input", nargs="+")
+    rp = sub.add_parser("probability", help="Markov log-probability of every record of a FASTA/FASTQ file under a .kdb profile (probability.py:36-151)")
+    rp.add_argument("--pseudocount", type=int, default=0, help="added to every count: k-mers the profile lacks then score finite")
+    rp.add_argument("--output-delimiter", default="\t")
+    rp.add_argument("--device", type=int, default=0)
+    rp.add_argument("seqfile", help="sequences to score, .fasta or .fastq (optionally gzipped)")
+    rp.add_argument("kdb", help="the k-mer profile (.kdb)")
+    return ap
+
+
+def main(argv=None):
+    """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
+    `graph`, `distance <metric> a.kdb b.kdb ...`, `matrix <method> a.kdb b.kdb ...`, `spectrum a.kdb ...` and
+    `probability <seqfile> <kdb>` beside it."""
+    ap = build_parser()
     a = ap.parse_args(argv)
+    if a.cmd == "probability":
+        from . import probability
+        probability.probabilities(a.seqfile, a.kdb, pseudocount=a.pseudocount, output_delimiter=a.output_delimiter, device=a.device)
+        return 0
     if a.cmd == "spectrum":
         from . import spectrum
         for p in a.input:
