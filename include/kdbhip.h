@@ -547,6 +547,12 @@ const char *kdb_prof_kernel_name(int kernel_id);
  *        is on.  Not used with "overlap" or "smallk_old", nor when the staging vector cannot be allocated),  "strand_merge_max_k" (1..17,
  *        default 12: the largest k that is staged; 13 stages k = 13's one-level path too -- 512 MiB, measured no faster --, and the two-level
  *        paths, k > "one_level_max_k", never are).  Setting either syncs first.
+ *        "one_level_defer" -1 / 0 / 2..64 (the one-level path, k = 9 .. "one_level_max_k": 0 sorts a batch's pages and adds them to the
+ *        vector right behind its scatter kernel; N keeps up to N scattered batches in a page arena -- about 2.05 bytes per residue of a
+ *        batch, within "pending_budget" / "reserve_bytes" like the arena of k >= 13 -- and adds them with one sort and one histogram pass:
+ *        when N are pending, when the next batch does not fit, and at kdb_sync; -1 (default): 4 for k <= 12, 0 for k = 13.  The vector
+ *        after a sync is the same either way, and as with "strand_merge" it is not written between syncs.  Where not even two batches fit,
+ *        batches are counted as with 0.  Not used with "overlap" or "algo" 1.  Setting it adds what is pending first.)
  *        The environment variable KDB_ENGINE_OPTS="name=value,..." sets options for every engine a process creates (experiments, the test
  *        suite under an option); an unknown name fails kdb_create.
  *   get: "sc_wide_lines", "l1_wide_lines", "l2_wide_lines", "l1_one_round", "reserve_bytes", "arena_budget_bytes" (what the arena may grow to, once decided), "free_at_sizing" (free device memory when it
@@ -557,8 +563,10 @@ const char *kdb_prof_kernel_name(int kernel_id);
  *        "arena_batches", "arena_pages" / "arena_reallocs" (size of the page arena in 1 KiB pages; times it was (re)allocated),
  *        "arena_cursor" / "arena_used_bound" / "arena_worst_case" (pages the pending batches hold: on the device, by the host's
  *        present bound, and by their worst cases added up), "one_level_max_k", "smallk_old", "strand_merge", "strand_merge_max_k",
- *        "hist_flushes" / "flushed_batches" / "full_flushes" (k >= 13: histogram passes over the arena, the batches they added
- *        to the vector, and how many of the passes a full arena forced), "bytes_in" and the
+ *        "hist_flushes" / "flushed_batches" / "full_flushes" (k >= 13, and "one_level_defer": histogram passes over the arena, the batches
+ *        they added to the vector, and how many of the passes a full arena forced), "one_level_defer", "one_level_pending" (batches the deferred
+ *        one-level path has scattered but not yet added; "pending_batches" counts those of k >= 13), "arena_region_base" (the arena page
+ *        at which the region of the next batch of the deferred one-level path would begin; 0: none pending), "bytes_in" and the
  *        device counters "pages_bases", "lines_bases", "pages_ids", "lines_ids", "table_bytes", "total_kmers" (what the
  *        kernels moved since kdb_reset, by their own count; reading one synchronises the compute stream).
  */

@@ -158,6 +158,7 @@ struct kdb_engine {
     hipStream_t s_hist = nullptr;
     kdb::OverlapState ov;
     kdb::TwoLevelPaged tp;            // its two-level form (k = 13..17): level-1 scratch and the arena of pending level-2 pages
+    kdb::OneLevelPending ol;          // the one-level path with option one_level_defer: the arena of batches scattered but not yet added to the vector
     int64_t oom_fallbacks = 0;        // batches that fell back to direct atomics because scratch did not fit
     // canonical engines, one-level LDS-histogram paths: batches count forward ids into d_fwd, kdb_sync adds both strands to d_table
     // at the canonical bins (kdb_strands.hip.h).  d_table itself is only ever added to, at canonical bins, as without the staging.
@@ -463,7 +464,9 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
             if (e->overlap && e->s_hist && !ex) rc = kdb::scatter_count_overlapped(e->ov, e->opt, e->s_compute, e->s_hist, batch, hook);
             if (rc == 3) {
                 { const int jrc = overlap_join(e); if (jrc != KDB_OK) return jrc; }
-                rc = kdb::scatter_count(e->sc, e->opt, e->s_compute, batch, hook);
+                // (one_level_defer: stage 2 waits for more batches; 3 = no room for an arena of two regions, and nothing is pending)
+                if (kdb::one_level_depth(e->opt, e->k) >= 2 && !(e->overlap && e->s_hist)) rc = kdb::scatter_count_deferred(e->ol, e->opt, e->s_compute, batch, hook);
+                if (rc == 3) rc = kdb::scatter_count(e->sc, e->opt, e->s_compute, batch, hook);
             }
         }
         else {
@@ -503,9 +506,13 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
     return KDB_OK;
 }
 
-// batches the two-level path has scattered into the page arena but not yet added to the vector
+// batches the two-level path, or the one-level path with one_level_defer, has scattered into a page arena but not yet added to the vector
 int flush_pending_paged(kdb_engine *e)
 {
+    if (e->ol.used) {
+        EngineProf hook(e);
+        if (kdb::one_level_flush(e->ol, e->s_compute, e->d_ctr, hook)) return fail(KDB_ERR_HIP, "LDS-histogram path failed: %s", kdb::partition_error());
+    }
     if (e->tp.pending == 0) return KDB_OK;
     EngineProf hook(e);
     if (kdb::twolevel_paged_flush(e->tp, e->opt, e->s_compute, e->d_table, e->d_ctr, hook)) return fail(KDB_ERR_HIP, "LDS-histogram path failed: %s", kdb::partition_error());
@@ -673,6 +680,8 @@ const OptRow OPTIONS[] = {
     {"reserve_bytes", KDB_OPT(opt.reserve_bytes), false, 0, INT64_MAX},
     {"arena_grow", KDB_OPT(opt.grow), false, 0, 2, OPT_NOTHING, " (0 never, 1 when it pays, 2 whenever the arena has filled up)"},
     {"arena_batches", KDB_OPT(opt.first_batches), false, 1, kdb::PAGED_PENDING_MAX, OPT_NOTHING, " (1..64: the arena's first size, in batches like the first one)"},
+    {"one_level_defer", KDB_OPT(opt.one_level_defer), false, -1, kdb::PAGED_PENDING_MAX, OPT_FLUSH_PENDING,
+     " (-1 = 4 for k <= 12 and 0 for k = 13, 0 = sort and histogram pass per batch, 2..64 = per that many batches)"},
     // what the engine reports
     {"k", KDB_OPT_RO(k)},
     {"arena_budget_bytes", [](kdb_engine *e) { return (int64_t)(e->opt.budget_bytes ? e->opt.budget_bytes : e->tp.budget_decided); }},
@@ -680,14 +689,17 @@ const OptRow OPTIONS[] = {
     {"overlap_scatter_grid", KDB_OPT_RO(ov.grid)},
     {"oom_fallbacks", KDB_OPT_RO(oom_fallbacks)},
     {"pending_batches", KDB_OPT_RO(tp.pending)},
+    {"one_level_pending", KDB_OPT_RO(ol.pending)},
     {"d2h_bytes", KDB_OPT_RO(d2h_bytes)},
     {"folded_files", KDB_OPT_RO(folded_files)},
     {"bytes_in", KDB_OPT_RO(bytes_in)},
-    {"arena_pages", KDB_OPT_RO(tp.arena.cap)},
-    {"arena_reallocs", KDB_OPT_RO(tp.reallocs)},
-    {"hist_flushes", KDB_OPT_RO(tp.flushes)},
-    {"flushed_batches", KDB_OPT_RO(tp.flushed_batches)},
-    {"full_flushes", KDB_OPT_RO(tp.full_flushes)},
+    // (an engine has one k: it fills the two-level arena or the one-level path's, and these count whichever it is)
+    {"arena_pages", [](kdb_engine *e) { return (int64_t)(e->tp.arena.cap + e->ol.arena.cap); }},
+    {"arena_reallocs", [](kdb_engine *e) { return (int64_t)(e->tp.reallocs + e->ol.reallocs); }},
+    {"hist_flushes", [](kdb_engine *e) { return (int64_t)(e->tp.flushes + e->ol.flushes); }},
+    {"flushed_batches", [](kdb_engine *e) { return (int64_t)(e->tp.flushed_batches + e->ol.flushed_batches); }},
+    {"full_flushes", [](kdb_engine *e) { return (int64_t)(e->tp.full_flushes + e->ol.full_flushes); }},
+    {"arena_region_base", KDB_OPT_RO(ol.used)},                   // the page the next one-level region would begin at (0: nothing pending)
 };
 #undef KDB_OPT
 #undef KDB_OPT_RO
@@ -811,6 +823,7 @@ int kdb_destroy(kdb_engine *e)
     kdb::overlap_free(e->ov);
     kdb::scatter_free(e->sc);
     kdb::twolevel_paged_free(e->tp);
+    kdb::one_level_free(e->ol);
     for (auto &s : e->spans) { (void)hipEventDestroy(s.a); (void)hipEventDestroy(s.b); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
     for (int b = 0; b < NBUF; b++) {
@@ -852,6 +865,7 @@ int kdb_reset(kdb_engine *e)
     DeviceGuard g(e->device);
     e->acc_nb = e->acc_nr = 0;                       // anything not yet counted is dropped with the vector
     kdb::twolevel_paged_drop(e->tp);
+    kdb::one_level_drop(e->ol);
     HIP_TRY(hipStreamSynchronize(e->s_copy));
     HIP_TRY(hipStreamSynchronize(e->s_compute));
     if (e->s_hist) { HIP_TRY(hipStreamSynchronize(e->s_hist)); e->ov.last = -1; }
@@ -2420,7 +2434,7 @@ int kdb_set_option(kdb_engine *e, const char *name, int64_t value)
         int rc = flush_pending_paged(e);
         if (rc != KDB_OK) return rc;
     }
-    if (!strcmp(name, "pending_budget")) e->tp.budget_decided = 0;      // (pending_budget = 0: the arena's size is decided anew at its next use)
+    if (!strcmp(name, "pending_budget")) e->tp.budget_decided = e->ol.budget_decided = 0;      // (pending_budget = 0: the arena's size is decided anew at its next use)
     if (row->before != OPT_SYNC_AND_STREAMS && row->before != OPT_SYNC) { row->set(e, row->boolean ? (value ? 1 : 0) : value); return KDB_OK; }
     DeviceGuard g(e->device);
     { int rc = kdb_sync(e); if (rc != KDB_OK) return rc; }

@@ -28,7 +28,13 @@ struct PagedOptions {
     size_t reserve_bytes = 0;              // device memory the arena must leave free whatever it grows to (RCCL's buffers and the reduce's scratch: kmerdb_amd/distributed.py)
     int grow = 1;                          // 0: the arena keeps its first size; 1: it doubles when that pays (arena_room); 2: whenever it has filled up
     int first_batches = 8;                 // the arena's first size, in batches like the first one (engine option arena_batches)
+    int one_level_defer = -1;              // the one-level path (k = 9 .. one_level_max_k): 0 = sort and histogram pass per batch; N >= 2 = once per N scattered batches
+                                           // (OneLevelPending); -1 = ONE_LEVEL_DEPTH for k <= 12, 0 for k = 13 (one_level_depth)
 };
+// Depth 4 takes 85 % of what depth 8 takes off the k = 12 headline step (-0.095 of 1.85 ms against -0.11; depth 2: -0.08) for half the arena, 12 GB for batches of
+// 10 M reads of 150 bases (profiles/one_level_defer_ab.txt).  k = 13 in one level keeps the immediate path unless asked: not measured.
+constexpr int ONE_LEVEL_DEPTH = 4;
+inline int one_level_depth(const PagedOptions &opt, int k) { return opt.one_level_defer >= 0 ? opt.one_level_defer : (k <= 12 ? ONE_LEVEL_DEPTH : 0); }
 
 // shared by every path: a set of pages, the sort of its tags, the histogram pass, the sizing of a sub-batch, the scatter kernels' launch
 // a set of pages with their tags, the page list that the sort of the tags makes, and the bucket arrays of that sort:
@@ -182,14 +188,17 @@ struct ScBatch {
 };
 
 // sub-batch L through a scatter_bases_kernel pair into the pages of `st`; the tags and the bucket counts that the page sort starts from are cleared first
+// (region >= 0: into the L.npages pages of `st` that begin at page `region` -- the kernels number their pages from the pointers they are given --,
+//  and nothing is cleared: the deferred one-level path clears tags and bucket counts once per flush)
 inline int launch_bases(const BasesPair &kp, hipStream_t stream, ProfHook &prof, const ScatterState &st, int nb, const ScLaunch &L, int contig_pages,
-                        const ScBatch &B, uint64_t t0, int ring_shift, int ring_bits, int sub_log2)
+                        const ScBatch &B, uint64_t t0, int ring_shift, int ring_bits, int sub_log2, int64_t region = -1)
 {
     ScOut out;
     out.pages = st.pages; out.tag = st.tag; out.extra_elems = L.extra_elems; out.wg_pages = L.wg_pages;
     out.wg_range = nullptr; out.contig = (uint32_t)contig_pages; out.wg_base = 0; out.grid = 0;
-    if (hipMemsetAsync(st.tag, 0xFF, (size_t)L.npages * sizeof(uint32_t), stream) != hipSuccess ||
-        hipMemsetAsync(st.d_bkt, 0, 2 * (size_t)nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+    if (region >= 0) { out.pages += (size_t)region * st.page_bytes; out.tag += (size_t)region; }
+    else if (hipMemsetAsync(st.tag, 0xFF, (size_t)L.npages * sizeof(uint32_t), stream) != hipSuccess ||
+             hipMemsetAsync(st.d_bkt, 0, 2 * (size_t)nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
     prof.begin_on(KDB_KERNEL_SCATTER, stream);
     for (BasesKernel fn : kp.fn)
         hipLaunchKernelGGL(fn, dim3(L.G), dim3(kp.threads), 0, stream, B.d_bases, (uint64_t)B.nbytes, (uint32_t)t0, L.nt, B.k, ring_shift, ring_bits, sub_log2, out,
@@ -282,6 +291,141 @@ inline int scatter_count(ScatterState &st, const PagedOptions &opt, hipStream_t 
         if (scatter_stage1(st, opt, stream, g, t0, B, prof, &L)) return 1;
         if (scatter_stage2(st, stream, g, L, B, prof)) return 1;
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------
+// The one-level path with stage 2 DEFERRED (option one_level_defer = N >= 2).  Stage 2 has a price that does not depend on the batch: every
+// workgroup of the pass locates its slice, zeroes 128 KiB of LDS and adds all 32768 counters of its bucket to the vector (a canonical engine
+// stages forward ids, so every bin of the 4^k vector is touched: the whole vector is read and written once per pass), and the sort and the pass
+// are four dependent dispatches behind two memsets.  None of that is needed while more batches are still to come: a batch's scatter kernel
+// writes into a region of its own in an arena, behind the regions of the batches already pending, and ONE sort of all their tags and ONE pass
+// add them to the vector -- when N batches are pending, when the next region does not fit, and at kdb_sync (which everything that reads the
+// vector goes through).  Scatter kernels and passes still never run side by side, and additions commute: the vector after a flush is what the
+// immediate path leaves, bit for bit.
+// ---------------------------------------------------------------------------------
+struct OneLevelPending {
+    ScatterState arena;
+    size_t used = 0;                       // pages of the regions handed out since the last flush: [0, used) is what the sort reads
+    size_t est_pages = 0;                  // pages those batches are expected to have filled (sizes the pass's slices, as scatter_stage2 does for one batch)
+    size_t tags_dirty = 0;                 // tags [0, tags_dirty) may have been written since they were last cleared
+    int pending = 0;                       // batches in the arena
+    // what the pending batches were scattered under; a batch that differs in any of it flushes them first
+    int k = 0, nb = 0, lo_bits = 0, hi_shift = 0; bool big = false;
+    unsigned long long *d_table = nullptr; // where their counts go (the vector, or a canonical engine's staging vector of forward counts)
+    size_t budget_decided = 0;             // the arena's budget where the option leaves it open, decided at first use (as TwoLevelPaged's)
+    bool grow_failed = false;              // an arena of the wanted size could not be allocated: no further attempts to enlarge it
+    uint64_t reallocs = 0, flushes = 0, flushed_batches = 0, full_flushes = 0;      // full_flushes: flushes because the next region did not fit
+};
+constexpr size_t ARENA_BYTES_PER_PAGE = SC_PAGE_BYTES + sizeof(uint32_t) + sizeof(PageEntry);      // a page, its tag, its list entry
+
+inline void one_level_free(OneLevelPending &ol) { scatter_free(ol.arena); ol = OneLevelPending(); }
+
+// kdb_reset / after a flush: no batch is pending any more (the tags are cleared when the next cycle begins)
+inline void one_level_drop(OneLevelPending &ol)
+{
+    if (ol.used > ol.tags_dirty) ol.tags_dirty = ol.used;
+    ol.used = 0; ol.est_pages = 0; ol.pending = 0;
+}
+
+// pages a sub-batch is expected to fill: two bytes per window position
+inline size_t one_level_est_pages(const ScGeom &g, const ScLaunch &L) { return (size_t)(((uint64_t)L.nt * g.tile_pos * 2) / SC_PAGE_BYTES) + 1u; }
+
+// one sort of every pending tag, one histogram pass
+inline int one_level_flush(OneLevelPending &ol, hipStream_t stream, DevCounters *d_ctr, ProfHook &prof)
+{
+    if (ol.used == 0) { one_level_drop(ol); return 0; }
+    // slices from the pending total: 512 workgroups in all, as for one batch, so that buckets of uniform input stay single-slice and flush
+    // without atomics; never 2^26 elements in a slice (the LDS counters are 32 bits wide, WRAP_MAX rests on it)
+    const size_t target = 512;
+    size_t slice_pages = (ol.est_pages + target - 1) / target;
+    if (slice_pages < 128) slice_pages = 128;
+    if (slice_pages > (1u << 17) - 1u) slice_pages = (1u << 17) - 1u;
+    if (hipMemsetAsync(ol.arena.d_bkt, 0, 2 * (size_t)ol.nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+    prof.begin_on(KDB_KERNEL_PAGE_SORT, stream);
+    page_sort(stream, ol.arena, (uint32_t)ol.used, (uint32_t)ol.nb, &d_ctr->pages_bases, 32u, (uint32_t)slice_pages, 256u, d_ctr);
+    prof.end();
+    prof.begin_on(KDB_KERNEL_PAGE_HIST, stream);
+    hist_pass(stream, ol.big, ol.arena, (uint32_t)ol.used, (uint32_t)ol.nb, (uint32_t)slice_pages, ol.d_table, ol.lo_bits, ol.hi_shift, 0, d_ctr);
+    prof.end();
+    ol.flushes++; ol.flushed_batches += (uint64_t)ol.pending;
+    one_level_drop(ol);
+    if (hipGetLastError() != hipSuccess) { partition_error_ref() = "histogram pass over the one-level arena failed to launch"; return 1; }
+    return 0;
+}
+
+// An arena that holds the region of `need` pages behind what is pending: flushes what is pending if the region does not fit, and (re)allocates
+// where the arena is missing, too small for two such regions, or smaller than `depth` of them when it has just filled up.
+// 0 ok, 1 error, 3 no room for two regions within the budget (nothing is pending then: the batch takes the immediate path)
+inline int one_level_room(OneLevelPending &ol, const PagedOptions &opt, hipStream_t stream, int depth, size_t need, size_t nb, DevCounters *d_ctr, ProfHook &prof)
+{
+    if (ol.arena.cap && ol.used + need <= ol.arena.cap && ol.arena.bkt_cap >= nb) return 0;
+    const bool filled_up = ol.used != 0;
+    if (filled_up) { ol.full_flushes++; if (one_level_flush(ol, stream, d_ctr, prof)) return 1; }
+    if (opt.budget_bytes == 0 && ol.budget_decided == 0) {
+        // as the two-level arena: 85 % of what is free at first use, less what the caller reserved
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        ol.budget_decided = free_b / 100 * 85;
+        if (opt.reserve_bytes && ol.budget_decided + opt.reserve_bytes > free_b) ol.budget_decided = free_b > opt.reserve_bytes ? free_b - opt.reserve_bytes : 0;
+        if (ol.budget_decided > (192ull << 30)) ol.budget_decided = 192ull << 30;
+        if (ol.budget_decided == 0) ol.budget_decided = 1;
+    }
+    size_t budget_pages = (opt.budget_bytes ? opt.budget_bytes : ol.budget_decided) / ARENA_BYTES_PER_PAGE;
+    if (ol.grow_failed && budget_pages > ol.arena.cap) budget_pages = ol.arena.cap;
+    size_t want = (size_t)depth * need;
+    if (want > budget_pages) want = budget_pages;
+    // a new arena if this one cannot hold two such regions, or if it has just filled up and one a quarter larger (at least) is wanted and allowed
+    const bool too_small = ol.arena.cap < 2 * need, grow = filled_up && want >= ol.arena.cap + ol.arena.cap / 4;
+    if (too_small || grow) {
+        // (only where it is too small: a quarter more than two regions is more than two.  What was free is asked again next time.)
+        if (want < 2 * need) { ol.budget_decided = 0; return 3; }
+        if (hipStreamSynchronize(stream) != hipSuccess) return reserve_error(1);
+        page_set_free(ol.arena);
+        ol.reallocs++;
+        if (page_set_alloc(ol.arena, want, SC_PAGE_BYTES) != 0) {
+            ol.grow_failed = true;                                      // (what could be had is the budget from now on)
+            if (page_set_alloc(ol.arena, 2 * need, SC_PAGE_BYTES) != 0) { ol.tags_dirty = 0; return 3; }
+        }
+        ol.tags_dirty = ol.arena.cap;
+    }
+    const int rc = bkt_reserve(ol.arena, stream, nb);
+    return rc == 2 ? 3 : rc;
+}
+
+// the tags a cycle begins with say "no page"
+inline int one_level_begin_cycle(OneLevelPending &ol, hipStream_t stream)
+{
+    if (ol.tags_dirty > ol.arena.cap) ol.tags_dirty = ol.arena.cap;
+    if (ol.tags_dirty && hipMemsetAsync(ol.arena.tag, 0xFF, ol.tags_dirty * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+    ol.tags_dirty = 0;
+    return 0;
+}
+
+// returns 0 ok (the batch is scattered; its counts reach the vector with the next flush), 1 error (partition_error()),
+// 3 no room for an arena of two regions (nothing of the batch was counted and nothing is pending): count it with scatter_count
+inline int scatter_count_deferred(OneLevelPending &ol, const PagedOptions &opt, hipStream_t stream, const ScBatch &B, ProfHook &prof)
+{
+    const ScGeom g = scatter_geometry(opt, B.nbytes, B.k);
+    const int depth = one_level_depth(opt, B.k);
+    if (ol.used && (ol.k != B.k || ol.nb != g.nb || ol.lo_bits != g.lo_bits || ol.hi_shift != g.hi_shift || ol.big != g.big || ol.d_table != B.d_table)) {
+        if (one_level_flush(ol, stream, B.d_ctr, prof)) return 1;
+    }
+    { const int rc = one_level_room(ol, opt, stream, depth, sub_batch(g, 0, B.n_expand).npages, (size_t)g.nb, B.d_ctr, prof); if (rc) return rc; }      // (the largest sub-batch)
+    ol.k = B.k; ol.nb = g.nb; ol.lo_bits = g.lo_bits; ol.hi_shift = g.hi_shift; ol.big = g.big; ol.d_table = B.d_table;
+    const BasesPair kp = select_one_level(g, B.k, B.n_expand, B.canonical);
+    for (uint64_t t0 = 0; t0 < g.ntiles_all; t0 += g.max_tiles) {
+        const ScLaunch L = sub_batch(g, t0, B.n_expand);
+        // (a later sub-batch of a batch of more than 2 Gi positions: the arena holds two of the largest, so after a flush it fits)
+        if (ol.used + L.npages > ol.arena.cap) { ol.full_flushes++; if (one_level_flush(ol, stream, B.d_ctr, prof)) return 1; }
+        if (ol.used == 0 && one_level_begin_cycle(ol, stream)) return 1;
+        if (launch_bases(kp, stream, prof, ol.arena, g.nb, L, opt.contig_pages, B, t0, g.lo_bits, g.nb_bits, g.sub_log2, (int64_t)ol.used)) return 1;
+        if (hipGetLastError() != hipSuccess) { partition_error_ref() = "paged scatter failed to launch"; return 1; }
+        ol.used += L.npages;
+        ol.est_pages += one_level_est_pages(g, L);
+    }
+    ol.pending++;
+    if (ol.pending >= depth) return one_level_flush(ol, stream, B.d_ctr, prof);
     return 0;
 }
 
