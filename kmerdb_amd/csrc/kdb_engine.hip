@@ -4,8 +4,6 @@
 // needs the device fails with KDB_ERR_HIP if HIP cannot provide one.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
-#include <cstdarg>
 #include <cstddef>
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +15,7 @@
 #include <vector>
 
 #include "../../include/kdbhip.h"
+#include "kdb_hostutil.hip.h"
 #include "kdb_kernels.hip.h"
 #include "kdb_hist.hip.h"
 #include "kdb_scatter.hip.h"
@@ -27,34 +26,12 @@
 #include "kdb_pairstats.hip.h"
 #include "kdb_sizefactors.hip.h"
 #include "kdb_spectrum.hip.h"
-#include "kdb_spectrum_host.cpp.h"
 #include "kdb_strands.hip.h"
 #include "kdb_score.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const char *fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t _e = (expr);                                                               \
-        if (_e != hipSuccess)                                                                 \
-            return fail(KDB_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),   \
-                        __FILE__, __LINE__);                                                  \
-    } while (0)
 
 constexpr int NBUF = 2;                                  // double-buffered staging
 const char *const KERNEL_NAMES[KDB_N_KERNELS] = {
@@ -189,12 +166,6 @@ struct kdb_engine {
 };
 
 namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
 
 hipEvent_t prof_event(kdb_engine *e)
 {
@@ -712,42 +683,6 @@ const OptRow *find_option(const char *name)
 }
 }  // namespace
 
-// kdb_gram: the launch of one group of rows, by the sizes of its blocks
-namespace {
-
-struct GramGroup { uint32_t row0, nrows; int na, nb; bool diag; };
-
-// the most workgroups per row of kdb_gram's and kdb_pairstats' sweeps (include/kdbhip.h)
-uint32_t gram_grid_max(uint32_t nrows) { return nrows < KDB_GRAM_GRID_MANY_ROWS ? (uint32_t)KDB_GRAM_GRID_MAX : (uint32_t)KDB_GRAM_GRID_MAX_MANY_ROWS; }
-
-void gram_launch(const GramGroup &gr, uint32_t gx, const unsigned long long *const *vecs, const kdbgram::Row *rows, uint32_t nchunks, uint32_t pstride, ulonglong2 *partials,
-                 hipStream_t st)
-{
-    const dim3 grid(gx, gr.nrows), block(kdbgram::TPB);
-    const kdbgram::Row *r = rows + gr.row0;
-    ulonglong2 *p = partials + (uint64_t)gr.row0 * pstride * kdbgram::NSLOT;
-#define KDB_GRAM_CASE(NA, NB, DIAG) hipLaunchKernelGGL((kdbgram::gram_kernel<NA, NB, DIAG>), grid, block, 0, st, vecs, r, nchunks, pstride, p)
-    if (gr.diag) {
-        switch (gr.na) {
-            case 1: KDB_GRAM_CASE(1, 1, true); break;
-            case 2: KDB_GRAM_CASE(2, 2, true); break;
-            case 3: KDB_GRAM_CASE(3, 3, true); break;
-            default: KDB_GRAM_CASE(4, 4, true); break;
-        }
-    } else {                                           // (off the diagonal the first block is always a full one)
-        switch (gr.nb) {
-            case 1: KDB_GRAM_CASE(4, 1, false); break;
-            case 2: KDB_GRAM_CASE(4, 2, false); break;
-            case 3: KDB_GRAM_CASE(4, 3, false); break;
-            default: KDB_GRAM_CASE(4, 4, false); break;
-        }
-    }
-#undef KDB_GRAM_CASE
-}
-
-}  // namespace
-
-
 extern "C" {
 
 int kdb_abi_version(void) { return KDB_ABI_VERSION; }
@@ -1203,625 +1138,6 @@ int kdb_nullomers(kdb_engine *e, int folded, uint64_t *ids_out, uint64_t cap, ui
     return KDB_OK;
 }
 
-// ---- exact moments of finished vectors (kdb_gram.hip.h): sums and Gram matrix as 128-bit integers ----
-int kdb_gram(int device_id, const void *const *d_vectors, int n, uint64_t nbins, uint64_t *sums_out, uint64_t *gram_out, double *kernel_ms_out)
-{
-    constexpr int B = kdbgram::B, NSLOT = kdbgram::NSLOT;
-    if (n < 1 || n > KDB_GRAM_MAX) return fail(KDB_ERR_ARG, "kdb_gram: n=%d, 1..%d vectors supported", n, KDB_GRAM_MAX);
-    if (nbins == 0 || nbins > (1ull << 36)) return fail(KDB_ERR_ARG, "kdb_gram: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)");
-    if (!d_vectors || !sums_out || !gram_out) return fail(KDB_ERR_ARG, "kdb_gram: d_vectors, sums_out and gram_out must not be NULL");
-    for (int i = 0; i < n; i++) {
-        if (!d_vectors[i]) return fail(KDB_ERR_ARG, "kdb_gram: vector %d is NULL", i);
-        if (((uintptr_t)d_vectors[i] & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_gram: vector %d is not 16-byte aligned", i);
-    }
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    DeviceGuard g(device_id);
-
-    // rows = pairs of blocks (bi <= bj), grouped by the kernel that serves them: the last block may hold fewer than B vectors
-    const int nblk = (n + B - 1) / B, last = n - (nblk - 1) * B, nfull = last == B ? nblk : nblk - 1;
-    std::vector<kdbgram::Row> rows;
-    std::vector<GramGroup> groups;
-    auto open_group = [&](int na, int nb, bool diag) { groups.push_back(GramGroup{(uint32_t)rows.size(), 0, na, nb, diag}); };
-    auto close_group = [&]() { groups.back().nrows = (uint32_t)rows.size() - groups.back().row0; if (!groups.back().nrows) groups.pop_back(); };
-    open_group(B, B, true);
-    for (int b = 0; b < nfull; b++) rows.push_back(kdbgram::Row{(uint8_t)b, (uint8_t)b});
-    close_group();
-    open_group(B, B, false);
-    for (int bi = 0; bi < nfull; bi++) for (int bj = bi + 1; bj < nfull; bj++) rows.push_back(kdbgram::Row{(uint8_t)bi, (uint8_t)bj});
-    close_group();
-    if (nfull < nblk) {
-        open_group(last, last, true);
-        rows.push_back(kdbgram::Row{(uint8_t)nfull, (uint8_t)nfull});
-        close_group();
-        open_group(B, last, false);
-        for (int bi = 0; bi < nfull; bi++) rows.push_back(kdbgram::Row{(uint8_t)bi, (uint8_t)nfull});
-        close_group();
-    }
-    const uint32_t nrows = (uint32_t)rows.size();
-    // gram_kernel takes the whole chunks, gram_tail_kernel the bins behind them; a row's partials: one per workgroup, then the tail's
-    const uint32_t nchunks = (uint32_t)(nbins / kdbgram::CHUNK_BINS), wg_chunks = kdbgram::TPB / 64;
-    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, gram_grid_max(nrows)));       // (any grid gives the same integers)
-    const uint32_t nparts = gx + 1;
-    struct Scratch {
-        const unsigned long long **vecs = nullptr; kdbgram::Row *rows = nullptr; ulonglong2 *partials = nullptr, *out = nullptr;
-        hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
-        ~Scratch()
-        {
-            (void)hipFree(vecs); (void)hipFree(rows); (void)hipFree(partials); (void)hipFree(out);
-            if (a) (void)hipEventDestroy(a);
-            if (b) (void)hipEventDestroy(b);
-            if (st) (void)hipStreamDestroy(st);
-        }
-    } sc;
-    std::vector<const unsigned long long *> ptrs((size_t)nblk * B, (const unsigned long long *)d_vectors[0]);
-    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
-    if (hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess || hipMalloc((void **)&sc.rows, nrows * sizeof(kdbgram::Row)) != hipSuccess ||
-        hipMalloc((void **)&sc.partials, (uint64_t)nrows * nparts * NSLOT * sizeof(ulonglong2)) != hipSuccess ||
-        hipMalloc((void **)&sc.out, (uint64_t)nrows * NSLOT * sizeof(ulonglong2)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_gram: no room for the partial sums of %u x %u workgroups", nrows, gx);
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc.a));
-    HIP_TRY(hipEventCreate(&sc.b));
-    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.rows, rows.data(), nrows * sizeof(kdbgram::Row), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    for (const GramGroup &gr : groups) gram_launch(gr, gx, sc.vecs, sc.rows, nchunks, nparts, sc.partials, sc.st);
-    hipLaunchKernelGGL(kdbgram::gram_tail_kernel, dim3(nrows), dim3(64), 0, sc.st, sc.vecs, (const kdbgram::Row *)sc.rows, n, (uint64_t)nchunks * kdbgram::CHUNK_BINS, nbins,
-                       nparts, gx, sc.partials);
-    hipLaunchKernelGGL(kdbgram::gram_combine_kernel, dim3(nrows), dim3(256), 0, sc.st, (const ulonglong2 *)sc.partials, nparts, sc.out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    std::vector<ulonglong2> res((size_t)nrows * NSLOT);
-    HIP_TRY(hipMemcpyAsync(res.data(), sc.out, res.size() * sizeof(ulonglong2), hipMemcpyDeviceToHost, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    if (kernel_ms_out) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
-        *kernel_ms_out = (double)ms;
-    }
-    for (uint32_t r = 0; r < nrows; r++) {
-        const ulonglong2 *slot = &res[(size_t)r * NSLOT];
-        for (int i = 0; i < B; i++) {
-            const int vi = rows[r].bi * B + i;
-            if (vi >= n) continue;
-            if (rows[r].bi == rows[r].bj) { sums_out[2 * vi] = slot[B * B + i].x; sums_out[2 * vi + 1] = slot[B * B + i].y; }
-            for (int j = 0; j < B; j++) {
-                const int vj = rows[r].bj * B + j;
-                if (vj >= n || vj < vi) continue;
-                const ulonglong2 v = slot[i * B + j];
-                gram_out[2 * ((size_t)vi * n + vj)] = gram_out[2 * ((size_t)vj * n + vi)] = v.x;
-                gram_out[2 * ((size_t)vi * n + vj) + 1] = gram_out[2 * ((size_t)vj * n + vi) + 1] = v.y;
-            }
-        }
-    }
-    for (int i = 0; i < n; i++)
-        if (sums_out[2 * i + 1] != 0)
-            return fail(KDB_ERR_ARG, "kdb_gram: the sum of vector %d is 2^64 or more: its products may have wrapped 128 bits", i);
-    return KDB_OK;
-}
-
-// ---- the pairwise statistics that are not moments (kdb_pairstats.hip.h): exact integers, and the float sweep of canberra / jensenshannon ----
-namespace {
-
-int pair_check_args(const char *who, const void *const *d_vectors, int n, uint64_t nbins)
-{
-    if (n < 1 || n > KDB_GRAM_MAX) return fail(KDB_ERR_ARG, "%s: n=%d, 1..%d vectors supported", who, n, KDB_GRAM_MAX);
-    if (nbins == 0 || nbins > kdbpair::NBINS_MAX) return fail(KDB_ERR_ARG, "%s: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)", who);
-    if (!d_vectors) return fail(KDB_ERR_ARG, "%s: d_vectors must not be NULL", who);
-    for (int i = 0; i < n; i++) {
-        if (!d_vectors[i]) return fail(KDB_ERR_ARG, "%s: vector %d is NULL", who, i);
-        if (((uintptr_t)d_vectors[i] & 15u) != 0) return fail(KDB_ERR_ARG, "%s: vector %d is not 16-byte aligned", who, i);
-    }
-    return KDB_OK;
-}
-
-struct PairGroup { uint32_t row0, nrows; int na, nb; bool diag; };
-
-void pair_launch(const PairGroup &gr, uint32_t gx, const unsigned long long *const *vecs, const kdbpair::Row *rows, uint32_t nchunks, uint32_t pstride,
-                 unsigned long long *partials, hipStream_t st)
-{
-    const dim3 grid(gx, gr.nrows), block(kdbpair::TPB);
-    const kdbpair::Row *r = rows + gr.row0;
-    unsigned long long *p = partials + (uint64_t)gr.row0 * pstride * kdbpair::ROW_WORDS;
-#define KDB_PAIR_CASE(NA, NB, DIAG) hipLaunchKernelGGL((kdbpair::pair_kernel<NA, NB, DIAG>), grid, block, 0, st, vecs, r, nchunks, pstride, p)
-    if (gr.diag) {
-        switch (gr.na) {
-            case 1: KDB_PAIR_CASE(1, 1, true); break;
-            case 2: KDB_PAIR_CASE(2, 2, true); break;
-            case 3: KDB_PAIR_CASE(3, 3, true); break;
-            default: KDB_PAIR_CASE(4, 4, true); break;
-        }
-    } else {                                           // (off the diagonal the first block is always a full one)
-        if (gr.nb == 1) KDB_PAIR_CASE(4, 1, false);
-        else KDB_PAIR_CASE(4, 2, false);
-    }
-#undef KDB_PAIR_CASE
-}
-
-struct PairScratch {
-    const unsigned long long **vecs = nullptr; void *rows = nullptr, *partials = nullptr, *out = nullptr; double *sums = nullptr;
-    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
-    ~PairScratch()
-    {
-        (void)hipFree(vecs); (void)hipFree(rows); (void)hipFree(partials); (void)hipFree(out); (void)hipFree(sums);
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
-}  // namespace
-
-int kdb_pairstats(int device_id, const void *const *d_vectors, int n, uint64_t nbins, uint64_t *sums_out, uint64_t *nnz_out, uint64_t *l1_out,
-                  uint64_t *linf_out, uint64_t *ne_out, uint64_t *both_out, double *kernel_ms_out)
-{
-    constexpr int B = kdbpair::B, HALF = kdbpair::HALF, NPAIR = kdbpair::NPAIR, PW = kdbpair::PAIR_WORDS, VW = kdbpair::VEC_WORDS, RW = kdbpair::ROW_WORDS;
-    if (int rc = pair_check_args("kdb_pairstats", d_vectors, n, nbins)) return rc;
-    if (!sums_out || !nnz_out || !l1_out || !linf_out || !ne_out || !both_out) return fail(KDB_ERR_ARG, "kdb_pairstats: the six output arrays must not be NULL");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    DeviceGuard g(device_id);
-
-    // rows, grouped by the kernel that serves them: the diagonal blocks (the last may hold fewer than B vectors), then every earlier block
-    // against the later blocks' vectors, HALF at a time
-    const int nblk = (n + B - 1) / B;
-    auto block_size = [&](int b) { return std::min(B, n - b * B); };
-    std::vector<kdbpair::Row> rows;
-    std::vector<PairGroup> groups;
-    auto push = [&](int a0, int na, int b0, int nb) {
-        const bool diag = a0 == b0;
-        if (groups.empty() || groups.back().na != na || groups.back().nb != nb || groups.back().diag != diag)
-            groups.push_back(PairGroup{(uint32_t)rows.size(), 0, na, nb, diag});
-        groups.back().nrows++;
-        rows.push_back(kdbpair::Row{(uint8_t)a0, (uint8_t)na, (uint8_t)b0, (uint8_t)nb});
-    };
-    for (int b = 0; b < nblk; b++) push(b * B, block_size(b), b * B, block_size(b));
-    for (int pass = 0; pass < 2; pass++)               // (rows of HALF vectors first, then the rows of a single one: two groups at most)
-        for (int bj = 1; bj < nblk; bj++)
-            for (int h = 0; h < block_size(bj); h += HALF) {
-                const int nb = std::min(HALF, block_size(bj) - h);
-                if ((nb == HALF) != (pass == 0)) continue;
-                for (int bi = 0; bi < bj; bi++) push(bi * B, B, bj * B + h, nb);
-            }
-    const uint32_t nrows = (uint32_t)rows.size();
-    // pair_kernel takes the whole chunks, pair_tail_kernel the bins behind them; a row's partials: one per workgroup, then the tail's
-    const uint32_t nchunks = (uint32_t)(nbins / kdbpair::CHUNK_BINS), wg_chunks = kdbpair::TPB / 64;
-    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, gram_grid_max(nrows)));       // (any grid gives the same integers)
-    const uint32_t nparts = gx + 1;
-    PairScratch sc;
-    std::vector<const unsigned long long *> ptrs((size_t)n);
-    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
-    if (hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess || hipMalloc(&sc.rows, nrows * sizeof(kdbpair::Row)) != hipSuccess ||
-        hipMalloc(&sc.partials, (uint64_t)nrows * nparts * RW * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc(&sc.out, (uint64_t)nrows * RW * sizeof(uint64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_pairstats: no room for the partial records of %u x %u workgroups", nrows, gx);
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc.a));
-    HIP_TRY(hipEventCreate(&sc.b));
-    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.rows, rows.data(), nrows * sizeof(kdbpair::Row), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    for (const PairGroup &gr : groups)
-        pair_launch(gr, gx, sc.vecs, (const kdbpair::Row *)sc.rows, nchunks, nparts, (unsigned long long *)sc.partials, sc.st);
-    hipLaunchKernelGGL(kdbpair::pair_tail_kernel, dim3(nrows), dim3(64), 0, sc.st, sc.vecs, (const kdbpair::Row *)sc.rows, (uint64_t)nchunks * kdbpair::CHUNK_BINS, nbins,
-                       nparts, gx, (unsigned long long *)sc.partials);
-    hipLaunchKernelGGL(kdbpair::pair_combine_kernel, dim3(nrows), dim3(256), 0, sc.st, (const unsigned long long *)sc.partials, nparts, (unsigned long long *)sc.out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    std::vector<unsigned long long> res((size_t)nrows * RW);
-    HIP_TRY(hipMemcpyAsync(res.data(), sc.out, res.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    if (kernel_ms_out) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
-        *kernel_ms_out = (double)ms;
-    }
-    for (uint32_t r = 0; r < nrows; r++) {
-        const unsigned long long *rec = &res[(size_t)r * RW];
-        const kdbpair::Row &row = rows[r];
-        const bool diag = row.a0 == row.b0;
-        for (int i = 0; i < row.na; i++) {
-            const size_t vi = (size_t)row.a0 + i;
-            if (diag) {
-                const unsigned long long *v = rec + NPAIR * PW + i * VW;
-                sums_out[2 * vi] = v[0]; sums_out[2 * vi + 1] = v[1]; nnz_out[vi] = v[2];
-                l1_out[2 * (vi * n + vi)] = l1_out[2 * (vi * n + vi) + 1] = linf_out[vi * n + vi] = ne_out[vi * n + vi] = 0;
-                both_out[vi * n + vi] = v[2];
-            }
-            for (int j = diag ? i + 1 : 0; j < row.nb; j++) {
-                const size_t vj = (size_t)row.b0 + j, at = vi * n + vj, ta = vj * n + vi;
-                const unsigned long long *p = rec + (i * B + j) * PW;
-                l1_out[2 * at] = l1_out[2 * ta] = p[0];
-                l1_out[2 * at + 1] = l1_out[2 * ta + 1] = p[1];
-                linf_out[at] = linf_out[ta] = p[2];
-                ne_out[at] = ne_out[ta] = p[3];
-                both_out[at] = both_out[ta] = p[4];
-            }
-        }
-    }
-    for (int i = 0; i < n; i++)
-        if (sums_out[2 * i + 1] != 0)
-            return fail(KDB_ERR_ARG, "kdb_pairstats: the sum of vector %d is 2^64 or more: L1 of a pair with it may not fit its two words", i);
-    return KDB_OK;
-}
-
-int kdb_pairfloat(int device_id, const void *const *d_vectors, int n, uint64_t nbins, double *canberra_out, double *js_out, double *kernel_ms_out)
-{
-    constexpr int FW = kdbpair::FLOAT_WORDS;
-    if (int rc = pair_check_args("kdb_pairfloat", d_vectors, n, nbins)) return rc;
-    if (!canberra_out || !js_out) return fail(KDB_ERR_ARG, "kdb_pairfloat: canberra_out and js_out must not be NULL");
-    // the exact sums (and the refusal of one that reaches 2^64), from the integer sweep
-    const size_t nn = (size_t)n * n;
-    std::vector<uint64_t> isums(2 * (size_t)n), scratch64(6 * nn + n);
-    if (int rc = kdb_pairstats(device_id, d_vectors, n, nbins, isums.data(), scratch64.data() + 6 * nn, scratch64.data(), scratch64.data() + 2 * nn,
-                               scratch64.data() + 3 * nn, scratch64.data() + 4 * nn, nullptr))
-        return rc;
-    std::vector<double> sums((size_t)n);
-    for (int i = 0; i < n; i++) sums[i] = (double)isums[2 * i];                       // (one rounding; the high word is zero)
-    for (size_t i = 0; i < nn; i++) canberra_out[i] = js_out[i] = 0.0;
-    if (kernel_ms_out) *kernel_ms_out = 0.0;
-    if (n < 2) return KDB_OK;
-    DeviceGuard g(device_id);
-
-    std::vector<kdbpair::FloatRow> rows;
-    for (int i = 0; i < n; i++) for (int j = i + 1; j < n; j++) rows.push_back(kdbpair::FloatRow{(uint8_t)i, (uint8_t)j});
-    const uint32_t nrows = (uint32_t)rows.size();
-    const uint32_t nchunks = (uint32_t)(nbins / kdbpair::CHUNK_BINS), wg_chunks = kdbpair::TPB / 64;
-    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, (uint32_t)KDB_PAIRFLOAT_GRID_MAX));          // (a function of nbins alone: the order of the additions is fixed)
-    const uint32_t nparts = gx + 1;
-    PairScratch sc;
-    std::vector<const unsigned long long *> ptrs((size_t)n);
-    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
-    if (hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess || hipMalloc(&sc.rows, nrows * sizeof(kdbpair::FloatRow)) != hipSuccess ||
-        hipMalloc((void **)&sc.sums, sums.size() * sizeof(double)) != hipSuccess ||
-        hipMalloc(&sc.partials, (uint64_t)nrows * nparts * FW * sizeof(double)) != hipSuccess ||
-        hipMalloc(&sc.out, (uint64_t)nrows * FW * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_pairfloat: no room for the partial sums of %u x %u workgroups", nrows, gx);
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc.a));
-    HIP_TRY(hipEventCreate(&sc.b));
-    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.rows, rows.data(), nrows * sizeof(kdbpair::FloatRow), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.sums, sums.data(), sums.size() * sizeof(double), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    hipLaunchKernelGGL(kdbpair::pairfloat_kernel, dim3(gx, nrows), dim3(kdbpair::TPB), 0, sc.st, sc.vecs, (const kdbpair::FloatRow *)sc.rows, (const double *)sc.sums, nchunks,
-                       nparts, (double *)sc.partials);
-    hipLaunchKernelGGL(kdbpair::pairfloat_tail_kernel, dim3(nrows), dim3(64), 0, sc.st, sc.vecs, (const kdbpair::FloatRow *)sc.rows, (const double *)sc.sums,
-                       (uint64_t)nchunks * kdbpair::CHUNK_BINS, nbins, nparts, gx, (double *)sc.partials);
-    hipLaunchKernelGGL(kdbpair::pairfloat_combine_kernel, dim3(nrows), dim3(64), 0, sc.st, (const double *)sc.partials, nparts, (double *)sc.out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    std::vector<double> res((size_t)nrows * FW);
-    HIP_TRY(hipMemcpyAsync(res.data(), sc.out, res.size() * sizeof(double), hipMemcpyDeviceToHost, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    if (kernel_ms_out) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
-        *kernel_ms_out = (double)ms;
-    }
-    for (uint32_t r = 0; r < nrows; r++) {
-        const size_t i = rows[r].i, j = rows[r].j;
-        const bool empty = isums[2 * i] == 0 || isums[2 * j] == 0;
-        canberra_out[i * n + j] = canberra_out[j * n + i] = res[(size_t)r * FW];
-        js_out[i * n + j] = js_out[j * n + i] = empty ? (double)NAN : res[(size_t)r * FW + 1];
-    }
-    return KDB_OK;
-}
-
-// ---- median-of-ratios size factors and normalised counts (kdb_sizefactors.hip.h, kdb_select_host.cpp.h) ----
-namespace {
-struct SizeFactorScratch {
-    const unsigned long long **vecs = nullptr; double *L = nullptr; unsigned long long *eligible = nullptr, *hist = nullptr; void *targets = nullptr;
-    uint32_t *flag = nullptr;
-    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
-    ~SizeFactorScratch()
-    {
-        (void)hipFree(vecs); (void)hipFree(L); (void)hipFree(eligible); (void)hipFree(hist); (void)hipFree(targets); (void)hipFree(flag);
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
-uint32_t sizefactor_grid(uint64_t nbins)
-{
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((nbins + kdbsf::WG_BINS - 1) / kdbsf::WG_BINS, kdbsf::MAX_GRID));
-}
-}  // namespace
-
-int kdb_size_factors(int device_id, const void *const *d_vectors, int n, uint64_t nbins, double *log_sf_out, uint64_t *eligible_out, double *kernel_ms_out)
-{
-    constexpr int NB = kdbsf::NBUCKET;
-    if (int rc = pair_check_args("kdb_size_factors", d_vectors, n, nbins)) return rc;
-    if (!log_sf_out || !eligible_out) return fail(KDB_ERR_ARG, "kdb_size_factors: log_sf_out and eligible_out must not be NULL");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    DeviceGuard g(device_id);
-
-    SizeFactorScratch sc;
-    std::vector<const unsigned long long *> ptrs((size_t)n);
-    for (int i = 0; i < n; i++) ptrs[i] = (const unsigned long long *)d_vectors[i];
-    const size_t hist_bytes = (size_t)n * 2 * NB * sizeof(uint64_t);
-    if (hipMalloc((void **)&sc.L, ((nbins + 1) & ~1ull) * sizeof(double)) != hipSuccess || hipMalloc((void **)&sc.vecs, ptrs.size() * sizeof(void *)) != hipSuccess ||
-        hipMalloc((void **)&sc.eligible, sizeof(uint64_t)) != hipSuccess || hipMalloc((void **)&sc.hist, hist_bytes) != hipSuccess ||
-        hipMalloc(&sc.targets, (size_t)n * sizeof(kdbsf::Target)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_size_factors: no room for the float64 scratch of %llu bins", (unsigned long long)nbins);
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc.a));
-    HIP_TRY(hipEventCreate(&sc.b));
-    const uint32_t gx = sizefactor_grid(nbins);                                        // (any grid gives the same integers)
-    double total_ms = 0.0;
-    auto add_elapsed = [&]() -> hipError_t {
-        float ms = 0;
-        const hipError_t e = hipEventElapsedTime(&ms, sc.a, sc.b);
-        total_ms += (double)ms;
-        return e;
-    };
-
-    uint64_t m = 0;
-    HIP_TRY(hipMemcpyAsync(sc.vecs, ptrs.data(), ptrs.size() * sizeof(void *), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemsetAsync(sc.eligible, 0, sizeof(uint64_t), sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    hipLaunchKernelGGL(kdbsf::geomean_kernel, dim3(gx), dim3(kdbsf::TPB), 0, sc.st, sc.vecs, n, nbins, sc.L, sc.eligible);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    HIP_TRY(hipMemcpyAsync(&m, sc.eligible, sizeof(uint64_t), hipMemcpyDeviceToHost, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    HIP_TRY(add_elapsed());
-    *eligible_out = m;
-    if (kernel_ms_out) *kernel_ms_out = total_ms;
-    if (m == 0) {
-        for (int j = 0; j < n; j++) log_sf_out[j] = (double)NAN;
-        return KDB_OK;
-    }
-
-    std::vector<kdbselect::Select> sel((size_t)n);
-    uint64_t lo, hi;
-    kdbselect::median_ranks(m, &lo, &hi);
-    for (auto &s : sel) s.start(lo, hi);
-    std::vector<kdbsf::Target> targets((size_t)n);
-    std::vector<uint64_t> hist((size_t)n * 2 * NB);
-    for (int pass = 0; pass < kdbselect::NPASS; pass++) {
-        for (int j = 0; j < n; j++) targets[j] = kdbsf::Target{{sel[j].prefix[0], sel[j].prefix[1]}, (uint32_t)sel[j].ntargets, 0};
-        HIP_TRY(hipMemcpyAsync(sc.targets, targets.data(), targets.size() * sizeof(kdbsf::Target), hipMemcpyHostToDevice, sc.st));
-        HIP_TRY(hipMemsetAsync(sc.hist, 0, hist_bytes, sc.st));
-        HIP_TRY(hipEventRecord(sc.a, sc.st));
-        hipLaunchKernelGGL(kdbsf::select_kernel, dim3(gx, (uint32_t)n), dim3(kdbsf::TPB), 0, sc.st, sc.vecs, (const double *)sc.L, nbins,
-                           (const kdbsf::Target *)sc.targets, kdbselect::pass_shift(pass), kdbselect::pass_width(pass), sc.hist);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(sc.b, sc.st));
-        HIP_TRY(hipMemcpyAsync(hist.data(), sc.hist, hist_bytes, hipMemcpyDeviceToHost, sc.st));
-        HIP_TRY(hipStreamSynchronize(sc.st));
-        HIP_TRY(add_elapsed());
-        for (int j = 0; j < n; j++)
-            if (!sel[j].step(&hist[(size_t)j * 2 * NB], &hist[(size_t)j * 2 * NB + NB], pass))
-                return fail(KDB_ERR_STATE, "kdb_size_factors: pass %d of the select found no element of the wanted rank in vector %d: the vectors changed during the call", pass, j);
-    }
-    for (int j = 0; j < n; j++) log_sf_out[j] = kdbselect::median_of(sel[j].low(), sel[j].high());
-    if (kernel_ms_out) *kernel_ms_out = total_ms;
-    return KDB_OK;
-}
-
-int kdb_scale_counts(int device_id, const void *d_vector, uint64_t nbins, double size_factor, void *d_out, int as_float64, double *kernel_ms_out)
-{
-    if (!d_vector || !d_out) return fail(KDB_ERR_ARG, "kdb_scale_counts: a vector is NULL");
-    if ((((uintptr_t)d_vector | (uintptr_t)d_out) & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_scale_counts: a vector is not 16-byte aligned");
-    if (nbins == 0 || nbins > kdbsf::NBINS_MAX) return fail(KDB_ERR_ARG, "kdb_scale_counts: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)");
-    if (!(size_factor > 0.0) || !std::isfinite(size_factor)) return fail(KDB_ERR_ARG, "kdb_scale_counts: the size factor %g is not finite and positive", size_factor);
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    DeviceGuard g(device_id);
-
-    SizeFactorScratch sc;
-    if (hipMalloc((void **)&sc.flag, sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_scale_counts: no room for the flag word");
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc.a));
-    HIP_TRY(hipEventCreate(&sc.b));
-    const uint32_t gx = sizefactor_grid(nbins);
-    const unsigned long long *x = (const unsigned long long *)d_vector;
-    uint32_t flag = 0;
-    HIP_TRY(hipMemsetAsync(sc.flag, 0, sizeof(uint32_t), sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    // x < 2^64 rounds to at most 2^64: only a size factor of 2 or less can bring a quotient to 2^63.  Then a first sweep looks and writes
-    // nothing, so that a refused call leaves d_out (which may be the input) as it was.
-    if (!as_float64 && size_factor <= 2.0) {
-        hipLaunchKernelGGL(kdbsf::scale_kernel, dim3(gx), dim3(kdbsf::TPB), 0, sc.st, x, nbins, size_factor, d_out, 0, 0, sc.flag);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(&flag, sc.flag, sizeof(uint32_t), hipMemcpyDeviceToHost, sc.st));
-        HIP_TRY(hipStreamSynchronize(sc.st));
-        if (flag != 0) return fail(KDB_ERR_ARG, "kdb_scale_counts: a count divided by the size factor %g reaches 2^63: it has no place in an int64 matrix", size_factor);
-    }
-    hipLaunchKernelGGL(kdbsf::scale_kernel, dim3(gx), dim3(kdbsf::TPB), 0, sc.st, x, nbins, size_factor, d_out, as_float64 ? 1 : 0, 1, sc.flag);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    if (kernel_ms_out) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
-        *kernel_ms_out = (double)ms;
-    }
-    return KDB_OK;
-}
-
-// ---- abundance spectrum and doubled mid-ranks of a finished vector (kdb_spectrum.hip.h, kdb_spectrum_host.cpp.h) ----
-namespace {
-struct SpectrumScratch {
-    unsigned long long *dense = nullptr;       // DENSE words, then the overflow list's counter
-    unsigned long long *over = nullptr;        // `cap` values
-    unsigned long long *tables = nullptr;      // kdb_rank_transform: the dense rank table, the distinct overflow values, their ranks
-    uint64_t cap = 0;
-    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
-    ~SpectrumScratch()
-    {
-        (void)hipFree(dense); (void)hipFree(over); (void)hipFree(tables);
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
-// what both entry points check first; nothing on the device is touched
-int spectrum_check_args(const char *who, int device_id, const void *d_vector, uint64_t nbins)
-{
-    if (!d_vector) return fail(KDB_ERR_ARG, "%s: the vector is NULL", who);
-    if (((uintptr_t)d_vector & 15u) != 0) return fail(KDB_ERR_ARG, "%s: the vector is not 16-byte aligned", who);
-    if (nbins == 0 || nbins > kdbspectrum::MAX_BINS) return fail(KDB_ERR_ARG, "%s: nbins is 0 or above 2^36 (64 x 4^17: more than a device holds)", who);
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    return KDB_OK;
-}
-
-// (re)allocate the list for `cap` values; the table, the stream and the events at the first call
-int spectrum_alloc(const char *who, SpectrumScratch &sc, uint64_t cap)
-{
-    if (!sc.dense && hipMalloc((void **)&sc.dense, (kdbspectrum::DENSE + 1) * 8ull) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "%s: no room for the table of %u multiplicities", who, kdbspectrum::DENSE);
-    }
-    (void)hipFree(sc.over);
-    sc.over = nullptr;
-    sc.cap = 0;
-    if (cap && hipMalloc((void **)&sc.over, cap * 8ull) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "%s: no room for a list of %llu values of 65536 and above", who, (unsigned long long)cap);
-    }
-    sc.cap = cap;
-    if (!sc.st) {
-        HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-        HIP_TRY(hipEventCreate(&sc.a));
-        HIP_TRY(hipEventCreate(&sc.b));
-    }
-    return KDB_OK;
-}
-
-// one sweep: host[0 .. DENSE) = the multiplicities, host[DENSE] = how many values the list would hold (sc.cap of them are stored); *ms += device time
-int spectrum_sweep(SpectrumScratch &sc, const void *d_vector, uint64_t nbins, std::vector<uint64_t> &host, double *ms)
-{
-    const uint64_t nchunks = nbins / kdbspectrum::CHUNK_BINS;
-    host.assign(kdbspectrum::DENSE + 1, 0);
-    HIP_TRY(hipMemsetAsync(sc.dense, 0, (kdbspectrum::DENSE + 1) * 8ull, sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    hipLaunchKernelGGL(kdbspectrum::spectrum_kernel, dim3(kdbspectrum::spectrum_grid(nchunks)), dim3(kdbspectrum::TPB), 0, sc.st,
-                       (const unsigned long long *)d_vector, nbins, nchunks, sc.dense, sc.over, (unsigned long long)sc.cap, sc.dense + kdbspectrum::DENSE);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    HIP_TRY(hipMemcpyAsync(host.data(), sc.dense, (kdbspectrum::DENSE + 1) * 8ull, hipMemcpyDeviceToHost, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    float t = 0;
-    HIP_TRY(hipEventElapsedTime(&t, sc.a, sc.b));
-    *ms += (double)t;
-    uint64_t total = host[kdbspectrum::DENSE];
-    for (uint32_t v = 0; v < kdbspectrum::DENSE; v++) total += host[v];
-    if (total != nbins) return fail(KDB_ERR_HIP, "the spectrum holds %llu bins, the vector %llu", (unsigned long long)total, (unsigned long long)nbins);
-    return KDB_OK;
-}
-}  // namespace
-
-int kdb_spectrum(int device_id, const void *d_vector, uint64_t nbins, uint64_t *dense_out, uint64_t *over_values_out, uint64_t over_cap,
-                 uint64_t *n_over_out, double *kernel_ms_out)
-{
-    if (n_over_out) *n_over_out = 0;
-    if (!dense_out || !n_over_out) return fail(KDB_ERR_ARG, "kdb_spectrum: dense_out and n_over_out must not be NULL");
-    int rc = spectrum_check_args("kdb_spectrum", device_id, d_vector, nbins);
-    if (rc != KDB_OK) return rc;
-    DeviceGuard g(device_id);
-    SpectrumScratch sc;
-    if ((rc = spectrum_alloc("kdb_spectrum", sc, over_values_out ? std::min(over_cap, nbins) : 0)) != KDB_OK) return rc;
-    std::vector<uint64_t> host;
-    double ms = 0;
-    if ((rc = spectrum_sweep(sc, d_vector, nbins, host, &ms)) != KDB_OK) return rc;
-    const uint64_t n_over = host[kdbspectrum::DENSE];
-    memcpy(dense_out, host.data(), kdbspectrum::DENSE * 8ull);
-    *n_over_out = n_over;
-    if (kernel_ms_out) *kernel_ms_out = ms;
-    if (!over_values_out || n_over == 0) return KDB_OK;
-    if (n_over > over_cap) return fail(KDB_ERR_ARG, "kdb_spectrum: %llu values of 65536 and above do not fit the %llu entries given", (unsigned long long)n_over, (unsigned long long)over_cap);
-    HIP_TRY(hipMemcpy(over_values_out, sc.over, n_over * 8ull, hipMemcpyDeviceToHost));
-    return KDB_OK;
-}
-
-int kdb_rank_transform(int device_id, const void *d_vector, uint64_t nbins, void *d_ranks_out, double *kernel_ms_out)
-{
-    if (nbins >= (1ull << 32)) return fail(KDB_ERR_ARG, "kdb_rank_transform: nbins is 2^32 or more (k >= 16): the doubled ranks sum to N (N + 1), which kdb_gram needs below 2^64");
-    if (!d_ranks_out || ((uintptr_t)d_ranks_out & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_rank_transform: the output is NULL or not 16-byte aligned");
-    int rc = spectrum_check_args("kdb_rank_transform", device_id, d_vector, nbins);
-    if (rc != KDB_OK) return rc;
-    DeviceGuard g(device_id);
-    SpectrumScratch sc;
-    std::vector<uint64_t> host;
-    double ms = 0;
-    // the list is short on count profiles (at most Sum counts / 65536 values): a first guess, and a second sweep with the exact length where it was wrong
-    if ((rc = spectrum_alloc("kdb_rank_transform", sc, std::min<uint64_t>(nbins, 1u << 20))) != KDB_OK) return rc;
-    if ((rc = spectrum_sweep(sc, d_vector, nbins, host, &ms)) != KDB_OK) return rc;
-    if (host[kdbspectrum::DENSE] > sc.cap) {
-        if ((rc = spectrum_alloc("kdb_rank_transform", sc, host[kdbspectrum::DENSE])) != KDB_OK) return rc;
-        if ((rc = spectrum_sweep(sc, d_vector, nbins, host, &ms)) != KDB_OK) return rc;
-        if (host[kdbspectrum::DENSE] > sc.cap) return fail(KDB_ERR_STATE, "kdb_rank_transform: the vector changed during the call");
-    }
-    const uint64_t n_over = host[kdbspectrum::DENSE];
-    std::vector<uint64_t> over(n_over);
-    if (n_over) HIP_TRY(hipMemcpy(over.data(), sc.over, n_over * 8ull, hipMemcpyDeviceToHost));
-    kdbspectrum_host::RankTables t;
-    kdbspectrum_host::rank_tables(host.data(), kdbspectrum::DENSE, over.data(), n_over, t);
-    if (t.nbins != nbins) return fail(KDB_ERR_HIP, "kdb_rank_transform: the rank tables cover %llu bins of %llu", (unsigned long long)t.nbins, (unsigned long long)nbins);
-    const uint64_t nd = t.over_values.size();
-    if (hipMalloc((void **)&sc.tables, (kdbspectrum::DENSE + 2 * nd) * 8ull) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_rank_transform: no room for the rank tables of %llu large values", (unsigned long long)nd);
-    }
-    HIP_TRY(hipMemcpyAsync(sc.tables, t.rank_dense.data(), kdbspectrum::DENSE * 8ull, hipMemcpyHostToDevice, sc.st));
-    if (nd) {
-        HIP_TRY(hipMemcpyAsync(sc.tables + kdbspectrum::DENSE, t.over_values.data(), nd * 8ull, hipMemcpyHostToDevice, sc.st));
-        HIP_TRY(hipMemcpyAsync(sc.tables + kdbspectrum::DENSE + nd, t.over_ranks.data(), nd * 8ull, hipMemcpyHostToDevice, sc.st));
-    }
-    const kdbspectrum::RankTables dt{sc.tables, sc.tables + kdbspectrum::DENSE, sc.tables + kdbspectrum::DENSE + nd, (uint32_t)nd};
-    const uint64_t nchunks = nbins / kdbspectrum::CHUNK_BINS;
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    hipLaunchKernelGGL(kdbspectrum::rank_map_kernel, dim3(kdbspectrum::spectrum_grid(nchunks)), dim3(kdbspectrum::TPB), 0, sc.st,
-                       (const unsigned long long *)d_vector, nbins, nchunks, dt, (unsigned long long *)d_ranks_out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    float tm = 0;
-    HIP_TRY(hipEventElapsedTime(&tm, sc.a, sc.b));
-    if (kernel_ms_out) *kernel_ms_out = ms + (double)tm;
-    return KDB_OK;
-}
-
-int kdb_strand_merge(int device_id, void *d_fwd, void *d_table, int k)
-{
-    if (k < 1 || k > 17) return fail(KDB_ERR_ARG, "kdb_strand_merge: k=%d outside 1..17", k);
-    if (!d_fwd || !d_table || d_fwd == d_table) return fail(KDB_ERR_ARG, "kdb_strand_merge: d_fwd and d_table must be two vectors");
-    if ((((uintptr_t)d_fwd | (uintptr_t)d_table) & 7u) != 0) return fail(KDB_ERR_ARG, "kdb_strand_merge: the vectors must be 8-byte aligned");
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    DeviceGuard g(device_id);
-    struct Stream { hipStream_t st = nullptr; ~Stream() { if (st) (void)hipStreamDestroy(st); } } s;
-    HIP_TRY(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-    kdbstrands::strand_merge_launch(s.st, (unsigned long long *)d_fwd, (unsigned long long *)d_table, k);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s.st));
-    return KDB_OK;
-}
-
 int kdb_reduce(kdb_engine *const *engines, int n, int root)
 {
     if (!engines || n < 2 || n > KDB_REDUCE_MAX) return fail(KDB_ERR_ARG, "kdb_reduce: n=%d engines (2..%d)", n, KDB_REDUCE_MAX);
@@ -2060,115 +1376,6 @@ int kdb_window_ids(kdb_engine *e, const uint8_t *bases, size_t nbytes, const uin
     if (c.bad_layout) return fail(KDB_ERR_ARG, "read_offsets must rise from 0 to nbytes");
     if (c.n_short) return fail(KDB_ERR_SHORT_READ, "%llu record(s) shorter than k=%d (reference: kmer.py:461-463 raises)", c.n_short, e->k);
     if (c.n_bad) return fail(KDB_ERR_BAD_RESIDUE, "%llu residue(s) outside ACGTN (reference: kmer.py:309 / :170 raises)", c.n_bad);
-    return KDB_OK;
-}
-
-// ---- reads scored against a profile (kdb_score.hip.h) ----
-namespace {
-struct ScoreScratch {
-    uint8_t *bases = nullptr; uint64_t *offs = nullptr; uint32_t *piece_rec = nullptr, *rec_piece0 = nullptr; kdbscore::PieceOut *pieces = nullptr;
-    kdb::DevCounters *ctr = nullptr; double *log10_p = nullptr; unsigned long long *ints = nullptr;
-    hipStream_t st = nullptr; hipEvent_t a = nullptr, b = nullptr;
-    ~ScoreScratch()
-    {
-        (void)hipFree(bases); (void)hipFree(offs); (void)hipFree(piece_rec); (void)hipFree(rec_piece0); (void)hipFree(pieces); (void)hipFree(ctr);
-        (void)hipFree(log10_p); (void)hipFree(ints);
-        if (a) (void)hipEventDestroy(a);
-        if (b) (void)hipEventDestroy(b);
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-}  // namespace
-
-int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, uint64_t total, uint64_t pseudocount, const uint8_t *bases, size_t nbytes,
-                    const uint64_t *offs, size_t nreads, int flags, double *log10_p_out, uint64_t *windows_out, uint64_t *zero_windows_out,
-                    uint64_t *min_count_out, double *kernel_ms_out)
-{
-    if (kernel_ms_out) *kernel_ms_out = 0.0;
-    if (k < 1 || k > 17) return fail(KDB_ERR_ARG, "kdb_score_reads: k=%d out of range 1..17", k);
-    if (!d_vector || ((uintptr_t)d_vector & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_score_reads: the vector is NULL or not 16-byte aligned");
-    if (flags & ~KDB_SCORE_CONTINUES) return fail(KDB_ERR_ARG, "kdb_score_reads: unknown flags %d", flags);
-    if (total == 0) return fail(KDB_ERR_ARG, "kdb_score_reads: total is 0 (an empty profile gives no probabilities)");
-    const uint64_t nbins = 1ull << (2 * k);
-    const unsigned __int128 total2 = (unsigned __int128)total + (unsigned __int128)pseudocount * nbins;
-    if ((total2 >> 64) != 0 || pseudocount >= (1ull << 62))
-        return fail(KDB_ERR_ARG, "kdb_score_reads: total + pseudocount * 4^k and 4 * pseudocount must stay below 2^64");
-    if (nreads == 0) return nbytes == 0 ? KDB_OK : fail(KDB_ERR_ARG, "kdb_score_reads: residues but no records");
-    if (!offs || (!bases && nbytes) || !log10_p_out || !windows_out || !zero_windows_out || !min_count_out) return fail(KDB_ERR_ARG, "kdb_score_reads: NULL buffer");
-    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_score_reads: at most 2^30 residues per call");
-    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_score_reads: at most 2^30 records per call");
-    const bool continues = (flags & KDB_SCORE_CONTINUES) != 0;
-    // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
-    if (offs[0] != 0 || offs[nreads] != nbytes) return fail(KDB_ERR_ARG, "read_offsets must start at 0 and end at nbytes");
-    std::vector<uint32_t> rec_piece0(nreads + 1);
-    uint64_t npieces = 0, nshort = 0;
-    for (size_t r = 0; r < nreads; r++) {
-        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return fail(KDB_ERR_ARG, "read_offsets must rise from 0 to nbytes");
-        const uint64_t len = offs[r + 1] - offs[r];
-        if (len < (uint64_t)k && !(r == 0 && continues)) nshort++;
-        const uint64_t nwin = len >= (uint64_t)k ? len - (uint64_t)k + 1 : 0;
-        rec_piece0[r] = (uint32_t)npieces;
-        npieces += std::max<uint64_t>(1, (nwin + kdbscore::PIECE - 1) / kdbscore::PIECE);         // (< 2^31: 2^30 records and 2^30 windows at most)
-    }
-    rec_piece0[nreads] = (uint32_t)npieces;
-    if (nshort) return fail(KDB_ERR_SHORT_READ, "%llu record(s) shorter than k=%d (reference: kmer.py:461-463 raises)", (unsigned long long)nshort, k);
-    std::vector<uint32_t> piece_rec;
-    if (npieces != nreads) {
-        piece_rec.resize(npieces);
-        for (size_t r = 0; r < nreads; r++)
-            for (uint32_t p = rec_piece0[r]; p < rec_piece0[r + 1]; p++) piece_rec[p] = (uint32_t)r;
-    }
-    int ndev = 0;
-    HIP_TRY(hipGetDeviceCount(&ndev));
-    if (device_id < 0 || device_id >= ndev) return fail(KDB_ERR_ARG, "device_id=%d but %d device(s) visible", device_id, ndev);
-    DeviceGuard g(device_id);
-
-    ScoreScratch sc;
-    if (hipMalloc((void **)&sc.bases, ((nbytes + 15) & ~(size_t)15) + 32) != hipSuccess /* (piece_kernel's aligned words reach 23 bytes past a window's start) */ || hipMalloc((void **)&sc.offs, (nreads + 1) * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc((void **)&sc.rec_piece0, (nreads + 1) * sizeof(uint32_t)) != hipSuccess ||
-        (!piece_rec.empty() && hipMalloc((void **)&sc.piece_rec, npieces * sizeof(uint32_t)) != hipSuccess) ||
-        hipMalloc((void **)&sc.pieces, npieces * sizeof(kdbscore::PieceOut)) != hipSuccess || hipMalloc((void **)&sc.ctr, sizeof(kdb::DevCounters)) != hipSuccess ||
-        hipMalloc((void **)&sc.log10_p, nreads * sizeof(double)) != hipSuccess || hipMalloc((void **)&sc.ints, 3 * nreads * sizeof(uint64_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(KDB_ERR_NOMEM, "kdb_score_reads: no room for the scratch of %zu residues in %zu records", nbytes, nreads);
-    }
-    HIP_TRY(hipStreamCreateWithFlags(&sc.st, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&sc.a));
-    HIP_TRY(hipEventCreate(&sc.b));
-    kdb::DevCounters c;
-    memset(&c, 0, sizeof c);
-    c.sus_count = 1;                       // more than sus_cap = 0: resolve_suspects_kernel judges every residue of the batch itself
-    if (nbytes) HIP_TRY(hipMemcpyAsync(sc.bases, bases, nbytes, hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.rec_piece0, rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, sc.st));
-    if (!piece_rec.empty()) HIP_TRY(hipMemcpyAsync(sc.piece_rec, piece_rec.data(), npieces * sizeof(uint32_t), hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipMemcpyAsync(sc.ctr, &c, sizeof c, hipMemcpyHostToDevice, sc.st));
-    HIP_TRY(hipEventRecord(sc.a, sc.st));
-    // what kdb_window_ids refuses: bytes with bit 7 set, letters outside ACGTN that no N shields (kmer.py:309 / :170)
-    hipLaunchKernelGGL(kdb::hibit_check_kernel, dim3(1024), dim3(256), 0, sc.st, (const uint8_t *)sc.bases, (uint64_t)nbytes, sc.ctr);
-    const unsigned check_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (nbytes / 64 + 255) / 256));
-    hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(check_grid), dim3(256), 0, sc.st, (const uint8_t *)sc.bases, (uint64_t)nbytes, (const uint64_t *)sc.offs,
-                       (uint64_t)nreads, k, sc.ctr);
-    unsigned long long *ints = sc.ints;
-    hipLaunchKernelGGL(kdbscore::piece_kernel, dim3((unsigned)((npieces + kdbscore::TPB / 64 - 1) / (kdbscore::TPB / 64))), dim3(kdbscore::TPB), 0, sc.st,
-                       (const uint8_t *)sc.bases, (const uint64_t *)sc.offs, (const uint32_t *)sc.piece_rec, (const uint32_t *)sc.rec_piece0, (uint32_t)npieces,
-                       (const unsigned long long *)d_vector, k, canonical ? 1 : 0, (unsigned long long)pseudocount, sc.pieces);
-    hipLaunchKernelGGL(kdbscore::record_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, sc.st, (const kdbscore::PieceOut *)sc.pieces,
-                       (const uint32_t *)sc.rec_piece0, (uint64_t)nreads, (double)(uint64_t)total2, continues ? 1 : 0, sc.log10_p, ints, ints + nreads, ints + 2 * nreads);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(sc.b, sc.st));
-    HIP_TRY(hipMemcpyAsync(&c, sc.ctr, sizeof c, hipMemcpyDeviceToHost, sc.st));
-    HIP_TRY(hipStreamSynchronize(sc.st));
-    if (kernel_ms_out) {
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, sc.a, sc.b));
-        *kernel_ms_out = (double)ms;
-    }
-    if (c.n_bad) return fail(KDB_ERR_BAD_RESIDUE, "%llu residue(s) outside ACGTN (reference: kmer.py:309 / :170 raises)", c.n_bad);
-    HIP_TRY(hipMemcpy(log10_p_out, sc.log10_p, nreads * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(windows_out, ints, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(zero_windows_out, ints + nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(min_count_out, ints + 2 * nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return KDB_OK;
 }
 
@@ -2485,3 +1692,6 @@ int kdb_get_option(kdb_engine *e, const char *name, int64_t *value)
 }
 
 }  // extern "C"
+
+// the analysis calls, which take finished vectors and no engine (here, behind the engine: their kernel templates are instantiated last)
+#include "kdb_analysis_host.hip.h"

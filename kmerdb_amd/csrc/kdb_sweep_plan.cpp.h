@@ -1,0 +1,126 @@
+// kdb_sweep_plan.cpp.h -- the host-only plans of the analysis calls (plain C++, no HIP: tests/c/sweep_plan_check.cpp compiles it alone, runs
+// it under the sanitizers and prints the plans for tests/sweep_cases.py to be compared with): which block pairs become which launch rows,
+// in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, and how the records of
+// kdb_score_reads split into pieces.  The block size, HALF, the chunk sizes and the piece size are arguments: the kernel headers have them.
+// A row type is the kernel header's (kdbgram::Row, kdbpair::Row, kdbpair::FloatRow) or any struct of as many uint8_t fields.
+#pragma once
+#include <cstdint>
+
+#include <algorithm>
+#include <vector>
+
+namespace kdbplan {
+
+// rows row0 .. row0 + nrows are one launch, of the instantiation <na, nb, diag>
+struct Group { uint32_t row0, nrows; int na, nb; bool diag; };
+
+template <class Row>
+struct Plan {
+    std::vector<Row> rows;
+    std::vector<Group> groups;
+    // a row joins the last group if that has its instantiation, else it opens one
+    void push(const Row &row, int na, int nb, bool diag)
+    {
+        if (groups.empty() || groups.back().na != na || groups.back().nb != nb || groups.back().diag != diag)
+            groups.push_back(Group{(uint32_t)rows.size(), 0, na, nb, diag});
+        groups.back().nrows++;
+        rows.push_back(row);
+    }
+};
+
+// kdb_gram: rows = pairs of blocks of B vectors (bi <= bj); the last block may hold fewer than B.  The full diagonal blocks, the pairs of
+// full blocks (bi-major), the short last block's diagonal, every full block against the short one.
+template <class Row>
+Plan<Row> gram_plan(int n, int B)
+{
+    const int nblk = (n + B - 1) / B, last = n - (nblk - 1) * B, nfull = last == B ? nblk : nblk - 1;
+    Plan<Row> p;
+    auto push = [&](int bi, int bj, int na, int nb) { p.push(Row{(uint8_t)bi, (uint8_t)bj}, na, nb, bi == bj); };
+    for (int b = 0; b < nfull; b++) push(b, b, B, B);
+    for (int bi = 0; bi < nfull; bi++) for (int bj = bi + 1; bj < nfull; bj++) push(bi, bj, B, B);
+    if (nfull < nblk) {
+        push(nfull, nfull, last, last);
+        for (int bi = 0; bi < nfull; bi++) push(bi, nfull, B, last);
+    }
+    return p;
+}
+
+// kdb_pairstats: rows = vectors a0 .. a0 + na against b0 .. b0 + nb.  The diagonal blocks (the last may hold fewer than B vectors), then
+// every earlier block against the later blocks' vectors, HALF at a time: the rows of HALF vectors first, then the rows of a single one
+// (two groups at most).
+template <class Row>
+Plan<Row> pair_plan(int n, int B, int HALF)
+{
+    const int nblk = (n + B - 1) / B;
+    auto block_size = [&](int b) { return std::min(B, n - b * B); };
+    Plan<Row> p;
+    auto push = [&](int a0, int na, int b0, int nb) { p.push(Row{(uint8_t)a0, (uint8_t)na, (uint8_t)b0, (uint8_t)nb}, na, nb, a0 == b0); };
+    for (int b = 0; b < nblk; b++) push(b * B, block_size(b), b * B, block_size(b));
+    for (int pass = 0; pass < 2; pass++)
+        for (int bj = 1; bj < nblk; bj++)
+            for (int h = 0; h < block_size(bj); h += HALF) {
+                const int nb = std::min(HALF, block_size(bj) - h);
+                if ((nb == HALF) != (pass == 0)) continue;
+                for (int bi = 0; bi < bj; bi++) push(bi * B, B, bj * B + h, nb);
+            }
+    return p;
+}
+
+// kdb_pairfloat: one pair i < j per row
+template <class Row>
+std::vector<Row> float_rows(int n)
+{
+    std::vector<Row> rows;
+    for (int i = 0; i < n; i++) for (int j = i + 1; j < n; j++) rows.push_back(Row{(uint8_t)i, (uint8_t)j});
+    return rows;
+}
+
+// The grid of a sweep whose waves step through chunks of chunk_bins bins, wg_chunks waves to a workgroup: gx workgroups per row, each with
+// a partial of its own.  tail: a tail kernel takes the bins behind the last whole chunk and writes one more partial (nparts = gx + 1);
+// without one the last, partial chunk is the body's.
+struct Grid { uint32_t nchunks, gx, nparts; };
+
+inline Grid sweep_grid(uint64_t nbins, uint32_t chunk_bins, uint32_t wg_chunks, uint32_t cap, bool tail = true)
+{
+    const uint32_t nchunks = (uint32_t)((nbins + (tail ? 0 : chunk_bins - 1)) / chunk_bins);
+    const uint32_t gx = std::max(1u, std::min((nchunks + wg_chunks - 1) / wg_chunks, cap));
+    return Grid{nchunks, gx, gx + 1};
+}
+
+// the most workgroups per row of a sweep with nrows rows: from many_rows rows on the rows fill the device and the smaller cap does
+inline uint32_t rows_cap(uint32_t nrows, uint32_t many_rows, uint32_t cap, uint32_t cap_many_rows) { return nrows < many_rows ? cap : cap_many_rows; }
+
+// kdb_score_reads: record r is pieces rec_piece0[r] .. rec_piece0[r + 1], of at most `piece` windows each and at least one (a record
+// without a window has an empty one); piece_rec[p] = the record of piece p, left empty when every record is one piece.  offs: nreads + 1
+// offsets into nbytes residues, nreads >= 1.  A record shorter than k counts as short unless it is the first and `continues` an earlier
+// call's; where there are short records piece_rec is left empty too: the caller refuses them.
+enum LayoutError { LAYOUT_OK = 0, LAYOUT_ENDS /* must start at 0 and end at nbytes */, LAYOUT_RISE /* must rise from 0 to nbytes */ };
+
+struct ScoreLayout {
+    std::vector<uint32_t> rec_piece0, piece_rec;
+    uint64_t npieces = 0, nshort = 0;
+};
+
+inline LayoutError score_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, int k, uint32_t piece, bool continues, ScoreLayout &lay)
+{
+    lay = ScoreLayout();
+    if (offs[0] != 0 || offs[nreads] != nbytes) return LAYOUT_ENDS;
+    lay.rec_piece0.resize(nreads + 1);
+    for (size_t r = 0; r < nreads; r++) {
+        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
+        const uint64_t len = offs[r + 1] - offs[r];
+        if (len < (uint64_t)k && !(r == 0 && continues)) lay.nshort++;
+        const uint64_t nwin = len >= (uint64_t)k ? len - (uint64_t)k + 1 : 0;
+        lay.rec_piece0[r] = (uint32_t)lay.npieces;
+        lay.npieces += std::max<uint64_t>(1, (nwin + piece - 1) / piece);         // (< 2^31: 2^30 records and 2^30 windows at most)
+    }
+    lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
+    if (lay.nshort == 0 && lay.npieces != nreads) {
+        lay.piece_rec.resize(lay.npieces);
+        for (size_t r = 0; r < nreads; r++)
+            for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
+    }
+    return LAYOUT_OK;
+}
+
+}  // namespace kdbplan

@@ -1,8 +1,9 @@
 """tests/sweep_cases.py proven on the CPU: the layout model agrees with the kernels' loops written out, the row grouping with the
-host code's, every case is where it claims to be, and the expected integers agree between two formulations.  No GPU."""
+host code's (run on the CPU), every case is where it claims to be, and the expected integers agree between two formulations.  No GPU."""
 import itertools
 import os
 import re
+import shutil
 import sys
 
 import numpy as np
@@ -10,10 +11,26 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import sweep_cases as sc  # noqa: E402
+import sweep_plan_program as prog  # noqa: E402
 
 ROOT = sc.ROOT
 TOP = sc.TOP
 WIDE = 2 ** 32
+
+
+# the files that hold the host code of the analysis sweeps: the entry points, their plans, and the engine they left
+HOST_FILES = ("kdb_analysis_host.hip.h", "kdb_sweep_plan.cpp.h", "kdb_hostutil.hip.h", "kdb_engine.hip")
+
+
+def _host_rows():
+    """{n: (gram rows, pair rows, float rows)} printed by tests/c/sweep_plan_check.cpp from the plan header the entry points use; under the
+    sanitizers where this g++ has them (tests/test_sweep_plan_host_sanitize.py is about that), plainly where not"""
+    try:
+        return prog.rows(sc.B, sc.HALF)
+    except prog.NoCompiler as e:
+        if shutil.which("g++") is None:
+            pytest.skip(str(e))
+        return prog.rows(sc.B, sc.HALF, sanitize=False)
 
 
 # ---- the constants, the map and the grouping ----
@@ -23,7 +40,7 @@ def test_the_grid_caps_are_the_headers_and_the_host_code_uses_them():
     for name in ("KDB_GRAM_GRID_MAX", "KDB_GRAM_GRID_MAX_MANY_ROWS", "KDB_GRAM_GRID_MANY_ROWS", "KDB_PAIRFLOAT_GRID_MAX", "KDB_SIZEFACTORS_GRID_MAX"):
         assert getattr(_abi, name) == sc.header_constant(name)
     assert (sc.GRID_MAX, sc.GRID_MAX_MANY, sc.MANY_ROWS, sc.FLOAT_GRID_MAX, sc.SF_GRID_MAX) == (1024, 256, 4, 512, 1024)
-    host = open(os.path.join(ROOT, "kmerdb_amd", "csrc", "kdb_engine.hip")).read()
+    host = "".join(open(os.path.join(ROOT, "kmerdb_amd", "csrc", f)).read() for f in HOST_FILES)
     assert not re.search(r"1024u\s*:\s*256u|wg_chunks,\s*512u", host)
     for name in ("KDB_GRAM_GRID_MAX", "KDB_GRAM_GRID_MAX_MANY_ROWS", "KDB_GRAM_GRID_MANY_ROWS", "KDB_PAIRFLOAT_GRID_MAX"):
         assert re.search(r"\b%s\b" % name, host), name
@@ -70,28 +87,12 @@ def test_the_map_is_the_kernels_loop(nbins, cap, tail):
     assert lay.second_stride().size == max(0, lay.body - 4 * lay.gx * 128)
 
 
-def _host_gram_rows(n):
-    """kdb_gram's host loop, line by line: (bi, bj) in order, with the group's template arguments"""
-    B = 4
-    nblk = (n + B - 1) // B
-    last = n - (nblk - 1) * B
-    nfull = nblk if last == B else nblk - 1
-    rows = [((B, B, True), b, b) for b in range(nfull)]
-    for bi in range(nfull):
-        for bj in range(bi + 1, nfull):
-            rows.append(((B, B, False), bi, bj))
-    if nfull < nblk:
-        rows.append(((last, last, True), nfull, nfull))
-        for bi in range(nfull):
-            rows.append(((B, last, False), bi, nfull))
-    return rows
-
-
 @pytest.mark.parametrize("n", list(range(1, 18)) + [64])
 def test_every_pair_has_one_row_and_its_instantiation(n):
     g, p = sc.gram_rows(n), sc.pair_rows(n)
-    host = _host_gram_rows(n)
-    assert [(r.inst, r.a[0] // 4, r.b[0] // 4) for r in g] == host
+    host_gram, host_pair, _ = _host_rows()[n]          # what the host code's own plan gives (kdb_sweep_plan.cpp.h, run on the CPU)
+    assert [tuple(r) for r in g] == host_gram
+    assert [tuple(r) for r in p] == host_pair
     nblk = -(-n // 4)
     assert len(g) == nblk * (nblk + 1) // 2
     assert len(p) == nblk + sum(bj * -(-min(4, n - 4 * bj) // 2) for bj in range(1, nblk))
