@@ -599,7 +599,7 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
     hipLaunchKernelGGL(kdb::hibit_check_kernel, dim3(1024), dim3(256), 0, call.st, (const uint8_t *)d_bases, (uint64_t)nbytes, ctr);
     const unsigned check_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (nbytes / 64 + 255) / 256));
     hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(check_grid), dim3(256), 0, call.st, (const uint8_t *)d_bases, (uint64_t)nbytes, (const uint64_t *)d_offs,
-                       (uint64_t)nreads, k, ctr);
+                       (uint64_t)nreads, k, ctr, 0);
     hipLaunchKernelGGL(kdbscore::piece_kernel, dim3((unsigned)((npieces + kdbscore::TPB / 64 - 1) / (kdbscore::TPB / 64))), dim3(kdbscore::TPB), 0, call.st,
                        (const uint8_t *)d_bases, (const uint64_t *)d_offs, (const uint32_t *)piece_rec, (const uint32_t *)rec_piece0, (uint32_t)npieces,
                        (const unsigned long long *)d_vector, k, canonical ? 1 : 0, (unsigned long long)pseudocount, pieces);

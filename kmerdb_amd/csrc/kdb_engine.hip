@@ -82,6 +82,7 @@ struct kdb_engine {
     bool owns_table = false;
     bool table_escaped = false;      // kdb_table handed the vector's address out: the caller may write it at any time
     kdb::DevCounters *d_ctr = nullptr;
+    bool batch_words_zero = false;                                    // the per-batch words of d_ctr are zero: kdb_reset, or the batch before ended in resolve_suspects_kernel
     unsigned long long *d_worklist = nullptr;        // EXPAND mode: windows with > 2 N's, expanded by a workgroup each
     size_t worklist_cap = 1u << 20;
     uint32_t *d_first_rec = nullptr; size_t first_rec_cap = 0;       // record that holds every 4096th byte of the batch in hand (lens_kernel)
@@ -392,8 +393,10 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
     {
         ProfScope ps(e, KDB_KERNEL_MARK);
         const dim3 grid((unsigned)((nreads + 255) / 256)), block(256);
-        // only the per-batch words: n_short, n_bad, bad_layout, not_uniform stay set until kdb_reset
-        HIP_TRY(hipMemsetAsync(&e->d_ctr->neg_min_len, 0, kdb::PER_BATCH_WORDS * sizeof(unsigned long long), e->s_compute));
+        // only the per-batch words: n_short, n_bad, bad_layout, not_uniform stay set until kdb_reset.  (Where the batch before ended in
+        // resolve_suspects_kernel, that kernel has left them zero: no memset, one dispatch less per batch.)
+        if (!e->batch_words_zero) HIP_TRY(hipMemsetAsync(&e->d_ctr->neg_min_len, 0, kdb::PER_BATCH_WORDS * sizeof(unsigned long long), e->s_compute));
+        e->batch_words_zero = false;
         const dim3 lgrid(grid.x < 1024u ? grid.x : 1024u);
         hipLaunchKernelGGL(kdb::lens_kernel, lgrid, block, 0, e->s_compute, d_offs, (uint64_t)nreads, (uint64_t)nbytes,
                            e->min_len > 0 ? e->min_len : e->k, first_is_continuation, e->d_ctr, e->d_first_rec);
@@ -471,7 +474,10 @@ int launch_batch(kdb_engine *e, uint8_t *d_bases, size_t nbytes, const uint64_t 
         // residues that are neither ACGT nor N: an IUPAC code is only an error in a window that no N shields (kmer.py:287-289)
         ProfScope ps(e, KDB_KERNEL_MARK);
         hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(4), dim3(256), 0, e->s_compute, (const uint8_t *)d_bases, (uint64_t)nbytes, d_offs, (uint64_t)nreads,
-                           e->k, e->d_ctr);
+                           e->k, e->d_ctr, 1);
+        HIP_TRY(hipGetLastError());
+        e->batch_words_zero = true;              // (the batch's last kernel: it puts the per-batch words back to zero)
+        return KDB_OK;
     }
     HIP_TRY(hipGetLastError());
     return KDB_OK;
@@ -810,6 +816,7 @@ int kdb_reset(kdb_engine *e)
     e->folded_files = e->folded_total = 0;
     e->tp.table_is_zero = e->owns_table && !e->table_escaped;             // (a caller-owned vector may be written by the caller at any time)
     HIP_TRY(hipMemsetAsync(e->d_ctr, 0, sizeof(kdb::DevCounters), e->s_compute));
+    e->batch_words_zero = true;
     unsigned long long wl[2] = {0, 0}, sus[2] = {0, 0};
     if (e->n_mode == KDB_N_EXPAND) {
         if (!e->d_worklist) HIP_TRY(hipMalloc((void **)&e->d_worklist, e->worklist_cap * sizeof(unsigned long long)));
@@ -1325,7 +1332,7 @@ int kdb_shred(kdb_engine *e, const uint8_t *seq, size_t nbytes, uint64_t *ids_ou
     hipLaunchKernelGGL(kdb::shred_kernel, dim3(ntiles), dim3(kdb::TPB), 0, e->s_compute, e->sh_seq, (uint64_t)nbytes, e->k,
                        e->canonical, e->sh_ids, e->sh_ctr);
     hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(1), dim3(256), 0, e->s_compute, (const uint8_t *)e->sh_seq, (uint64_t)nbytes, (const uint64_t *)nullptr,
-                       (uint64_t)1, e->k, e->sh_ctr);
+                       (uint64_t)1, e->k, e->sh_ctr, 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ids.data(), e->sh_ids, nbytes * 8ull, hipMemcpyDeviceToHost, e->s_compute));
     HIP_TRY(hipMemcpyAsync(&c, e->sh_ctr, sizeof c, hipMemcpyDeviceToHost, e->s_compute));
@@ -1368,7 +1375,7 @@ int kdb_window_ids(kdb_engine *e, const uint8_t *bases, size_t nbytes, const uin
     hipLaunchKernelGGL(kdb::shred_kernel, dim3(ntiles), dim3(kdb::TPB), 0, e->s_compute, e->sh_seq, (uint64_t)nbytes, e->k,
                        e->canonical, e->sh_ids, e->sh_ctr);
     hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(4), dim3(256), 0, e->s_compute, (const uint8_t *)e->sh_seq, (uint64_t)nbytes, (const uint64_t *)e->sh_offs,
-                       (uint64_t)nreads, e->k, e->sh_ctr);
+                       (uint64_t)nreads, e->k, e->sh_ctr, 0);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ids_out, e->sh_ids, nbytes * 8ull, hipMemcpyDeviceToHost, e->s_compute));
     HIP_TRY(hipMemcpyAsync(&c, e->sh_ctr, sizeof c, hipMemcpyDeviceToHost, e->s_compute));

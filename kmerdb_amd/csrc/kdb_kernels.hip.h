@@ -49,7 +49,8 @@ struct DevCounters {
     unsigned long long pages_bases, lines_bases;     // written by scatter_bases_kernel (read by scatter_ids_kernel or page_hist_kernel)
     unsigned long long pages_ids, lines_ids;         // written by scatter_ids_kernel (read by page_hist_kernel)
     unsigned long long table_bytes;                  // page_hist_kernel: bytes of the count vector read + written
-    // per-batch record geometry (PER_BATCH_WORDS words zeroed before every batch, filled by lens_kernel)
+    // per-batch record geometry (PER_BATCH_WORDS words, zero before every batch and filled by lens_kernel: cleared by the last kernel of the batch before,
+    // resolve_suspects_kernel, where one ran -- by a memset otherwise)
     unsigned long long neg_min_len;     // max over records of ~len  (== ~min len)
     unsigned long long max_len;         // max record length; ~0 if the batch must use start marks
     unsigned long long wl_count;        // N-windows queued for expand_worklist_kernel in this batch (may exceed wl_cap)
@@ -64,6 +65,7 @@ struct DevCounters {
     // ids instead of adding them to the vector itself -- the histogram pass of the batch BEFORE runs beside it and updates its bins
     // with plain read-modify-writes.  [0] = entries appended, [1] = capacity, then the pairs; apply_hot_kernel adds them, in hist order.
     unsigned long long *hot_side;
+    unsigned int tail_ticket;           // resolve_suspects_kernel as a batch's last kernel: workgroups that are through with the per-batch words (zero between launches)
 };
 constexpr int PER_BATCH_WORDS = 4;      // neg_min_len, max_len, wl_count, sus_count
 
@@ -312,8 +314,9 @@ __device__ __forceinline__ bool suspect_is_bad(const uint8_t *__restrict__ bases
 
 __global__ void __launch_bounds__(256)
 resolve_suspects_kernel(const uint8_t *__restrict__ bases, uint64_t nbytes, const uint64_t *__restrict__ offs /* null: one record */, uint64_t nreads,
-                        int k, DevCounters *ctr)
+                        int k, DevCounters *ctr, int last_of_batch /* nothing reads the per-batch words after this launch: leave them zero for the next batch */)
 {
+    __shared__ unsigned int s_last;
     const unsigned long long listed = ctr->sus_count;
     const unsigned long long tid = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x, nthreads = (unsigned long long)gridDim.x * blockDim.x;
     unsigned long long bad = 0;
@@ -349,6 +352,16 @@ resolve_suspects_kernel(const uint8_t *__restrict__ bases, uint64_t nbytes, cons
             }
     }
     if (bad) __hip_atomic_fetch_add(&ctr->n_bad, bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!last_of_batch) return;
+    // The per-batch words go back to zero here, so that no memset has to run in front of the next batch's lens_kernel: the workgroup that draws the
+    // last ticket knows that all the others have read sus_count and the list, and never waits for them.
+    __syncthreads();
+    if (threadIdx.x == 0) s_last = __hip_atomic_fetch_add(&ctr->tail_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u;
+    __syncthreads();
+    if (s_last && threadIdx.x == 0) {
+        ctr->neg_min_len = 0; ctr->max_len = 0; ctr->wl_count = 0; ctr->sus_count = 0;
+        __hip_atomic_store(&ctr->tail_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // 4 words whose bytes are 0x00 / 0x80 -> 16-bit mask, bit (4q+b) = byte b of word q.

@@ -1348,22 +1348,73 @@ scatter_ids_kernel(const uint8_t *__restrict__ pages1, const PageEntry *__restri
 // ---------------------------------------------------------------------------------
 // pages per bucket and elements per bucket.  Every workgroup takes a contiguous chunk of page numbers and counts it
 // in LDS first: global atomics on a few hundred addresses would serialise at the memory side (2.3 ms for 3 M pages,
-// measured; 0.04 ms this way).  The LDS counters cover a WINDOW of PAGES_LDS_NB buckets that starts at the smallest
-// bucket of the chunk: with up to 2^18 final buckets (two-level path) a chunk of the arena still holds the pages of a
-// few workgroups, i.e. of a few leading digits (x 512 buckets each); a tag outside the window takes a global atomic.
+// measured; 0.04 ms this way).  Two forms:
+//   direct   (nb <= PAGES_DIRECT_NB: every one-level k and level 1): the LDS counters cover all buckets.  The count kernel adds a
+//            workgroup's counts to bkt_pages with one atomic per bucket and keeps what the atomic returned -- where the workgroup's
+//            pages of that bucket begin inside the bucket's list -- in row blockIdx.x of a matrix of gridDim.x x nb words; the place
+//            kernel starts its LDS cursors from page_base + that row.  It neither counts its chunk again nor touches bkt_pages:
+//            the tags are read twice in all.
+//   windowed (the two-level arena's up to 2^18 buckets): the LDS counters cover a WINDOW of PAGES_LDS_NB buckets that starts at
+//            the smallest bucket of the chunk -- a chunk of the arena holds the pages of a few workgroups, i.e. of a few leading
+//            digits (x 512 buckets each); a tag outside the window takes a global atomic.  The place kernel counts its chunk again
+//            and reserves its ranges by counting bkt_pages down.
+// Both forms leave everything as the next sort wants to find it: the place kernel, the tags' last reader, writes SC_NO_PAGE over
+// every tag that says anything else; bkt_elems is zeroed by the scan, its last reader; bkt_pages by the scan (direct) or by being
+// counted down to zero (windowed).  Tags are read four at a time (16 bytes; chunks are multiples of four tags), two loads in flight.
 constexpr int PAGES_LDS_NB = 4096;
+constexpr int PAGES_DIRECT_NB = 1024;    // most buckets of the direct form
+constexpr int PAGES_DIRECT_GRID = 256;   // most workgroups of the direct form (rows of the matrix)
 constexpr int PAGES_THREADS = 1024;
 
+__device__ __forceinline__ void pages_chunk(uint32_t npages, uint32_t *p0, uint32_t *p1)
+{
+    const uint64_t chunk = (((uint64_t)npages + gridDim.x - 1) / gridDim.x + 3ull) & ~3ull, a = (uint64_t)blockIdx.x * chunk;
+    *p0 = (uint32_t)(a < npages ? a : npages);
+    *p1 = (uint32_t)(a + chunk < npages ? a + chunk : npages);
+}
+
+// tags [p, p + 4) of a chunk that ends at p1 (p a multiple of four, p < p1); SC_NO_PAGE for those at and beyond p1
+__device__ __forceinline__ uint4 pages_load4(const uint32_t *tag, uint32_t p, uint32_t p1)
+{
+    if (p1 - p >= 4u) return *reinterpret_cast<const uint4 *>(tag + p);
+    uint4 v = make_uint4(tag[p], SC_NO_PAGE, SC_NO_PAGE, SC_NO_PAGE);
+    if (p1 - p > 1u) v.y = tag[p + 1];
+    if (p1 - p > 2u) v.z = tag[p + 2];
+    return v;
+}
+
+// one(p, t) for every tag of [p0, p1) (also for tags that say "no page"); RESTORE: tags that say anything else are overwritten with SC_NO_PAGE
+template <bool RESTORE, typename TAGP, typename F>
+__device__ __forceinline__ void pages_sweep(TAGP tag, uint32_t p0, uint32_t p1, F &&one)
+{
+    auto quad = [&](uint32_t p, const uint4 &v) {
+        one(p, v.x); one(p + 1u, v.y); one(p + 2u, v.z); one(p + 3u, v.w);
+        if constexpr (RESTORE) {
+            if ((v.x & v.y & v.z & v.w) != SC_NO_PAGE) {
+                if (p1 - p >= 4u) *reinterpret_cast<uint4 *>(tag + p) = make_uint4(SC_NO_PAGE, SC_NO_PAGE, SC_NO_PAGE, SC_NO_PAGE);
+                else for (uint32_t i = 0; i < p1 - p; i++) tag[p + i] = SC_NO_PAGE;
+            }
+        }
+    };
+    for (uint32_t p = p0 + 4u * threadIdx.x; p < p1; p += 8u * PAGES_THREADS) {
+        const uint32_t q = p + 4u * PAGES_THREADS;
+        const bool two = q < p1;
+        const uint4 a = pages_load4(tag, p, p1);
+        const uint4 b = two ? pages_load4(tag, q, p1) : make_uint4(SC_NO_PAGE, SC_NO_PAGE, SC_NO_PAGE, SC_NO_PAGE);
+        quad(p, a);
+        if (two) quad(q, b);
+    }
+}
+
 // smallest bucket among the valid tags of [p0, p1) (block-wide; 0xFFFFFFFF if none)
-__device__ __forceinline__ uint32_t pages_window_start(const uint32_t *__restrict__ tag, uint32_t p0, uint32_t p1, uint32_t *s_min)
+__device__ __forceinline__ uint32_t pages_window_start(const uint32_t *tag, uint32_t p0, uint32_t p1, uint32_t *s_min)
 {
     if (threadIdx.x == 0) *s_min = 0xFFFFFFFFu;
     __syncthreads();
     uint32_t m = 0xFFFFFFFFu;
-    for (uint32_t p = p0 + threadIdx.x; p < p1; p += PAGES_THREADS) {
-        const uint32_t t = tag[p];
+    pages_sweep<false>(tag, p0, p1, [&](uint32_t, uint32_t t) {
         if (t != SC_NO_PAGE && (t & ((1u << SC_TAG_SHIFT) - 1u))) { const uint32_t b = t >> SC_TAG_SHIFT; m = b < m ? b : m; }
-    }
+    });
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const uint32_t x = (uint32_t)__shfl_xor((int)m, o, 64); m = x < m ? x : m; }
     if ((threadIdx.x & 63) == 0 && m != 0xFFFFFFFFu) atomicMin(s_min, m);
@@ -1371,36 +1422,46 @@ __device__ __forceinline__ uint32_t pages_window_start(const uint32_t *__restric
     return *s_min;
 }
 
+template <bool WINDOW>
 __global__ void __launch_bounds__(PAGES_THREADS)
 pages_count_kernel(const uint32_t *__restrict__ tag, uint32_t npages, uint32_t nb, uint32_t *__restrict__ bkt_pages, uint32_t *__restrict__ bkt_elems,
+                   uint32_t *__restrict__ wg_off /* direct form: [gridDim.x][nb] */,
                    unsigned long long *__restrict__ stat /* {pages with elements, lines written into them} += ; may be null */, uint32_t line_elems)
 {
-    __shared__ uint32_t cp[PAGES_LDS_NB], ce[PAGES_LDS_NB];
+    __shared__ unsigned long long cpe[PAGES_LDS_NB];             // pages << 32 | elements (a chunk's elements stay far below 2^32): one LDS atomic per page
     __shared__ uint32_t s_min, s_pages, s_lines;
-    const uint32_t chunk = (npages + gridDim.x - 1) / gridDim.x, p0 = blockIdx.x * chunk, p1 = p0 + chunk < npages ? p0 + chunk : npages;
-    const uint32_t w0 = pages_window_start(tag, p0, p1, &s_min);
-    if (w0 == 0xFFFFFFFFu) return;
-    for (uint32_t b = threadIdx.x; b < (uint32_t)PAGES_LDS_NB; b += PAGES_THREADS) { cp[b] = 0; ce[b] = 0; }
+    uint32_t p0, p1;
+    pages_chunk(npages, &p0, &p1);
+    uint32_t w0 = 0;
+    if constexpr (WINDOW) {
+        w0 = pages_window_start(tag, p0, p1, &s_min);
+        if (w0 == 0xFFFFFFFFu) return;
+    }
+    const uint32_t nw = WINDOW ? (uint32_t)PAGES_LDS_NB : nb;
+    for (uint32_t b = threadIdx.x; b < nw; b += PAGES_THREADS) cpe[b] = 0;
     if (threadIdx.x == 0) { s_pages = 0; s_lines = 0; }
     __syncthreads();
     uint32_t my_pages = 0, my_lines = 0;
-    for (uint32_t p = p0 + threadIdx.x; p < p1; p += PAGES_THREADS) {
-        const uint32_t t = tag[p];
-        if (t == SC_NO_PAGE) continue;
+    pages_sweep<false>(tag, p0, p1, [&](uint32_t, uint32_t t) {
+        if (t == SC_NO_PAGE) return;
         const uint32_t b = t >> SC_TAG_SHIFT, n = t & ((1u << SC_TAG_SHIFT) - 1u);
-        if (n == 0) continue;
+        if (n == 0) return;
         my_pages++; my_lines += (n + line_elems - 1u) / line_elems;
-        if (b - w0 < (uint32_t)PAGES_LDS_NB) { atomicAdd(&cp[b - w0], 1u); atomicAdd(&ce[b - w0], n); }
-        else { atomicAdd(&bkt_pages[b], 1u); atomicAdd(&bkt_elems[b], n); }
-    }
+        if (b - w0 < nw) atomicAdd(&cpe[b - w0], (1ull << 32) | n);
+        else if (WINDOW) { atomicAdd(&bkt_pages[b], 1u); atomicAdd(&bkt_elems[b], n); }
+    });
     if (stat) {
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) { my_pages += (uint32_t)__shfl_xor((int)my_pages, o, 64); my_lines += (uint32_t)__shfl_xor((int)my_lines, o, 64); }
         if ((threadIdx.x & 63) == 0 && my_pages) { atomicAdd(&s_pages, my_pages); atomicAdd(&s_lines, my_lines); }
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < (uint32_t)PAGES_LDS_NB && w0 + b < nb; b += PAGES_THREADS)
-        if (cp[b]) { atomicAdd(&bkt_pages[w0 + b], cp[b]); atomicAdd(&bkt_elems[w0 + b], ce[b]); }
+    for (uint32_t b = threadIdx.x; b < nw && w0 + b < nb; b += PAGES_THREADS) {
+        const uint32_t cp = (uint32_t)(cpe[b] >> 32), ce = (uint32_t)cpe[b];
+        uint32_t off = 0;
+        if (cp) { off = atomicAdd(&bkt_pages[w0 + b], cp); atomicAdd(&bkt_elems[w0 + b], ce); }
+        if constexpr (!WINDOW) wg_off[(size_t)blockIdx.x * nb + b] = off;
+    }
     if (stat && threadIdx.x == 0 && s_pages) {
         __hip_atomic_fetch_add(&stat[0], (unsigned long long)s_pages, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_fetch_add(&stat[1], (unsigned long long)s_lines, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1408,10 +1469,11 @@ pages_count_kernel(const uint32_t *__restrict__ tag, uint32_t npages, uint32_t n
 }
 
 // exclusive scan of the page counts (one workgroup; nb <= 1024 * per-thread loop) -> page_base[nb + 1], P2 slice table
-// (slices ~ pages), Sum(elements) -> total_kmers
+// (slices ~ pages), Sum(elements) -> total_kmers.  The last reader of bkt_elems, and in the direct form (zero_pages) of bkt_pages:
+// it leaves them zero for the next sort.
 __global__ void __launch_bounds__(1024)
-pages_scan_kernel(const uint32_t *__restrict__ bkt_pages, const uint32_t *__restrict__ bkt_elems, uint32_t nb,
-                  uint32_t *__restrict__ page_base, uint32_t *__restrict__ slice_base, uint32_t slice_pages, DevCounters *ctr)
+pages_scan_kernel(uint32_t *__restrict__ bkt_pages, uint32_t *__restrict__ bkt_elems, uint32_t nb,
+                  uint32_t *__restrict__ page_base, uint32_t *__restrict__ slice_base, uint32_t slice_pages, int zero_pages, DevCounters *ctr)
 {
     __shared__ uint32_t wsum[1024 / 64];
     __shared__ unsigned long long s_tot;
@@ -1421,7 +1483,11 @@ pages_scan_kernel(const uint32_t *__restrict__ bkt_pages, const uint32_t *__rest
     const uint32_t lo = j * per < nb ? j * per : nb, hi = lo + per < nb ? lo + per : nb;
     uint32_t sum = 0, ssum = 0;
     unsigned long long el = 0;
-    for (uint32_t i = lo; i < hi; i++) { const uint32_t v = bkt_pages[i]; sum += v; ssum += (v + slice_pages - 1) / slice_pages; el += bkt_elems[i]; }
+    for (uint32_t i = lo; i < hi; i++) {
+        const uint32_t v = bkt_pages[i], n = bkt_elems[i];
+        sum += v; ssum += (v + slice_pages - 1) / slice_pages; el += n;
+        if (n) bkt_elems[i] = 0;
+    }
     uint32_t tot, stot;
     uint32_t run = block_excl_scan<1024>(sum, wsum, &tot);
     uint32_t srun = block_excl_scan<1024>(ssum, wsum, &stot);
@@ -1429,6 +1495,7 @@ pages_scan_kernel(const uint32_t *__restrict__ bkt_pages, const uint32_t *__rest
         const uint32_t v = bkt_pages[i];
         page_base[i] = run; slice_base[i] = srun;
         run += v; srun += (v + slice_pages - 1) / slice_pages;
+        if (zero_pages && v) bkt_pages[i] = 0;
     }
     el = wave_sum(el);
     if ((j & 63) == 0 && el) atomicAdd(&s_tot, el);
@@ -1439,39 +1506,50 @@ pages_scan_kernel(const uint32_t *__restrict__ bkt_pages, const uint32_t *__rest
     }
 }
 
-// page p -> its place in the list of its bucket (bkt_pages counts down; the order inside a bucket does not matter).
-// Same chunking and window: a workgroup reserves, per bucket, one range for all its pages of that bucket, and fills it
-// from LDS cursors.
+// page p -> its place in the list of its bucket (the order inside a bucket does not matter), from LDS cursors: one range per
+// workgroup and bucket.  Direct form: the range begins where the count kernel's atomic said (wg_off).  Windowed form: same chunking
+// and window as the count kernel; the workgroup counts its chunk again and reserves its ranges by counting bkt_pages down.
+// Every tag that does not say "no page" -- pages without elements too, and in chunks without any page -- is set to SC_NO_PAGE.
+template <bool WINDOW>
 __global__ void __launch_bounds__(PAGES_THREADS)
-pages_place_kernel(const uint32_t *__restrict__ tag, uint32_t npages, uint32_t nb, uint32_t *__restrict__ bkt_pages, const uint32_t *__restrict__ page_base,
-                   PageEntry *__restrict__ list)
+pages_place_kernel(uint32_t *tag, uint32_t npages, uint32_t nb, uint32_t *__restrict__ bkt_pages, const uint32_t *__restrict__ page_base,
+                   const uint32_t *__restrict__ wg_off, PageEntry *__restrict__ list)
 {
     __shared__ uint32_t cur[PAGES_LDS_NB];
     __shared__ uint32_t s_min;
-    const uint32_t chunk = (npages + gridDim.x - 1) / gridDim.x, p0 = blockIdx.x * chunk, p1 = p0 + chunk < npages ? p0 + chunk : npages;
-    const uint32_t w0 = pages_window_start(tag, p0, p1, &s_min);
-    if (w0 == 0xFFFFFFFFu) return;
-    for (uint32_t b = threadIdx.x; b < (uint32_t)PAGES_LDS_NB; b += PAGES_THREADS) cur[b] = 0;
-    __syncthreads();
-    for (uint32_t p = p0 + threadIdx.x; p < p1; p += PAGES_THREADS) {
-        const uint32_t t = tag[p];
-        if (t != SC_NO_PAGE && (t & ((1u << SC_TAG_SHIFT) - 1u)) && (t >> SC_TAG_SHIFT) - w0 < (uint32_t)PAGES_LDS_NB) atomicAdd(&cur[(t >> SC_TAG_SHIFT) - w0], 1u);
+    uint32_t p0, p1;
+    pages_chunk(npages, &p0, &p1);
+    uint32_t w0 = 0;
+    if constexpr (WINDOW) {
+        w0 = pages_window_start(tag, p0, p1, &s_min);
+        if (w0 != 0xFFFFFFFFu) {                                        // (block-uniform)
+            for (uint32_t b = threadIdx.x; b < (uint32_t)PAGES_LDS_NB; b += PAGES_THREADS) cur[b] = 0;
+            __syncthreads();
+            pages_sweep<false>((const uint32_t *)tag, p0, p1, [&](uint32_t, uint32_t t) {
+                if (t != SC_NO_PAGE && (t & ((1u << SC_TAG_SHIFT) - 1u)) && (t >> SC_TAG_SHIFT) - w0 < (uint32_t)PAGES_LDS_NB) atomicAdd(&cur[(t >> SC_TAG_SHIFT) - w0], 1u);
+            });
+            __syncthreads();
+            for (uint32_t b = threadIdx.x; b < (uint32_t)PAGES_LDS_NB && w0 + b < nb; b += PAGES_THREADS) {
+                const uint32_t c = cur[b];
+                if (c) cur[b] = page_base[w0 + b] + atomicSub(&bkt_pages[w0 + b], c) - c;
+            }
+        }
+    }
+    else {
+        for (uint32_t b = threadIdx.x; b < nb; b += PAGES_THREADS) cur[b] = page_base[b] + wg_off[(size_t)blockIdx.x * nb + b];
     }
     __syncthreads();
-    for (uint32_t b = threadIdx.x; b < (uint32_t)PAGES_LDS_NB && w0 + b < nb; b += PAGES_THREADS) {
-        const uint32_t c = cur[b];
-        if (c) cur[b] = page_base[w0 + b] + atomicSub(&bkt_pages[w0 + b], c) - c;
-    }
-    __syncthreads();
-    for (uint32_t p = p0 + threadIdx.x; p < p1; p += PAGES_THREADS) {
-        const uint32_t t = tag[p];
-        if (t == SC_NO_PAGE) continue;
+    const uint32_t nw = WINDOW ? (uint32_t)PAGES_LDS_NB : nb;
+    pages_sweep<true>(tag, p0, p1, [&](uint32_t p, uint32_t t) {      // (no page with elements in a windowed chunk: w0 is not looked at)
+        if (t == SC_NO_PAGE) return;
         const uint32_t b = t >> SC_TAG_SHIFT, n = t & ((1u << SC_TAG_SHIFT) - 1u);
-        if (n == 0) continue;
-        const uint32_t pos = b - w0 < (uint32_t)PAGES_LDS_NB ? atomicAdd(&cur[b - w0], 1u) : page_base[b] + atomicSub(&bkt_pages[b], 1u) - 1u;
-        list[pos].page = p;
-        list[pos].nelems = n;
-    }
+        if (n == 0) return;
+        uint32_t pos;
+        if (b - w0 < nw) pos = atomicAdd(&cur[b - w0], 1u);
+        else if (WINDOW) pos = page_base[b] + atomicSub(&bkt_pages[b], 1u) - 1u;
+        else return;                                                     // (a bucket that does not exist: the scatter kernels write none)
+        *reinterpret_cast<uint2 *>(&list[pos]) = make_uint2(p, n);      // (PageEntry {page, nelems} in one store)
+    });
 }
 
 // ---------------------------------------------------------------------------------

@@ -44,6 +44,10 @@ struct ScatterState {
     uint32_t *tag = nullptr;                                    // [cap]
     PageEntry *list = nullptr;                                  // [cap]
     uint32_t *d_bkt = nullptr; size_t bkt_cap = 0;              // bkt_arrays for bkt_cap buckets
+    // What a page sort starts from -- unused pages' tags say "no page", bucket counts are zero -- is also what it leaves behind (the place kernel
+    // restores the tags it reads, the scan zeroes the counts), so the memsets run only for what is not known to be clean:
+    size_t tags_dirty = 0;                                      // tags [0, tags_dirty) may hold something else: a new page set, pages written but never sorted
+    size_t bkt_zero_nb = 0;                                     // bkt_pages and bkt_elems are zero as laid out for this many buckets (0: not known)
 };
 
 inline void page_set_free(ScatterState &st)
@@ -51,14 +55,14 @@ inline void page_set_free(ScatterState &st)
     if (st.pages) (void)hipFree(st.pages);
     if (st.tag) (void)hipFree(st.tag);
     if (st.list) (void)hipFree(st.list);
-    st.pages = nullptr; st.tag = nullptr; st.list = nullptr; st.cap = 0;
+    st.pages = nullptr; st.tag = nullptr; st.list = nullptr; st.cap = 0; st.tags_dirty = 0;
 }
 
 // pages, tags and list for npages; 0 ok, 2 no room (no page set is held then); the old set must have been freed
 inline int page_set_alloc(ScatterState &st, size_t npages, size_t page_bytes)
 {
     if (hipMalloc((void **)&st.pages, npages * page_bytes) == hipSuccess && hipMalloc((void **)&st.tag, npages * sizeof(uint32_t)) == hipSuccess &&
-        hipMalloc((void **)&st.list, npages * sizeof(PageEntry)) == hipSuccess) { st.cap = npages; st.page_bytes = page_bytes; return 0; }
+        hipMalloc((void **)&st.list, npages * sizeof(PageEntry)) == hipSuccess) { st.cap = npages; st.page_bytes = page_bytes; st.tags_dirty = npages; return 0; }
     (void)hipGetLastError();
     page_set_free(st);
     return 2;
@@ -71,9 +75,11 @@ inline void scatter_free(ScatterState &st)
     st = ScatterState();
 }
 
-// the bucket arrays, one allocation of 4 nb + 2 words: bkt_pages [nb] | bkt_elems [nb] | page_base [nb + 1] | slice_base [nb + 1]
-struct BktArrays { uint32_t *pages, *elems, *page_base, *slice_base; };
-inline BktArrays bkt_arrays(const ScatterState &st, size_t nb) { return {st.d_bkt, st.d_bkt + nb, st.d_bkt + 2 * nb, st.d_bkt + 3 * nb + 1}; }
+// the bucket arrays, one allocation: bkt_pages [nb] | bkt_elems [nb] | page_base [nb + 1] | slice_base [nb + 1] | and, for the direct form of
+// the sort (nb <= PAGES_DIRECT_NB), wg_off [PAGES_DIRECT_GRID][nb]
+struct BktArrays { uint32_t *pages, *elems, *page_base, *slice_base, *wg_off; };
+inline BktArrays bkt_arrays(const ScatterState &st, size_t nb) { return {st.d_bkt, st.d_bkt + nb, st.d_bkt + 2 * nb, st.d_bkt + 3 * nb + 1, st.d_bkt + 4 * nb + 2}; }
+inline size_t bkt_words(size_t nb) { return 4 * nb + 2 + (nb <= (size_t)PAGES_DIRECT_NB ? (size_t)PAGES_DIRECT_GRID * nb : 0); }
 
 inline int reserve_error(int rc) { if (rc) partition_error_ref() = rc == 2 ? "scratch allocation failed" : "stream error"; return rc; }
 
@@ -82,7 +88,10 @@ inline int bkt_reserve(ScatterState &st, hipStream_t stream, size_t nb)
 {
     if (st.bkt_cap >= nb) return 0;
     if (st.d_bkt) { if (hipStreamSynchronize(stream) != hipSuccess) return reserve_error(1); (void)hipFree(st.d_bkt); st.d_bkt = nullptr; st.bkt_cap = 0; }
-    if (hipMalloc((void **)&st.d_bkt, (4 * nb + 2) * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return reserve_error(2); }
+    st.bkt_zero_nb = 0;
+    size_t words = bkt_words(nb);          // (room for every layout of up to nb buckets: the direct form's is largest at PAGES_DIRECT_NB)
+    if (nb > (size_t)PAGES_DIRECT_NB && words < bkt_words((size_t)PAGES_DIRECT_NB)) words = bkt_words((size_t)PAGES_DIRECT_NB);
+    if (hipMalloc((void **)&st.d_bkt, words * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); return reserve_error(2); }
     st.bkt_cap = nb;
     return 0;
 }
@@ -97,17 +106,38 @@ inline int scatter_reserve(ScatterState &st, hipStream_t stream, size_t npages, 
     return bkt_reserve(st, stream, nb);
 }
 
-// the page sort: a counting sort of the first `npages` tags into one page list per bucket, histogram slices of `slice_pages` pages
-inline void page_sort(hipStream_t stream, const ScatterState &st, uint32_t npages, uint32_t nb, unsigned long long *stat, uint32_t line_elems, uint32_t slice_pages,
-                      uint32_t grid_cap, DevCounters *scan_ctr)
+// before pages of `st` are written: the tags not known to say "no page" are cleared (a new page set; pages written and dropped before a sort read them)
+inline int tags_clean(ScatterState &st, hipStream_t stream)
+{
+    if (st.tags_dirty > st.cap) st.tags_dirty = st.cap;
+    if (st.tags_dirty && hipMemsetAsync(st.tag, 0xFF, st.tags_dirty * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+    st.tags_dirty = 0;
+    return 0;
+}
+
+// the page sort: a counting sort of the first `npages` tags into one page list per bucket, histogram slices of `slice_pages` pages.
+// It leaves those tags saying "no page" and the bucket counts zero (kdb_scatter.hip.h); the counts are cleared here where that is not known.
+inline int page_sort(hipStream_t stream, ScatterState &st, uint32_t npages, uint32_t nb, unsigned long long *stat, uint32_t line_elems, uint32_t slice_pages,
+                     uint32_t grid_cap, DevCounters *scan_ctr)
 {
     const BktArrays b = bkt_arrays(st, nb);
+    if (st.bkt_zero_nb != nb) {
+        st.bkt_zero_nb = 0;
+        if (hipMemsetAsync(st.d_bkt, 0, 2 * (size_t)nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+    }
+    const bool direct = nb <= (uint32_t)PAGES_DIRECT_NB;
+    if (direct && grid_cap > (uint32_t)PAGES_DIRECT_GRID) grid_cap = (uint32_t)PAGES_DIRECT_GRID;
     const uint32_t pgrid = (npages + 4095u) / 4096u < grid_cap ? (npages + 4095u) / 4096u : grid_cap;
-    hipLaunchKernelGGL(pages_count_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)st.tag, npages, nb, b.pages, b.elems, stat, line_elems);
-    hipLaunchKernelGGL(pages_scan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t *)b.pages, (const uint32_t *)b.elems, nb, b.page_base, b.slice_base,
-                       slice_pages, scan_ctr);
-    hipLaunchKernelGGL(pages_place_kernel, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)st.tag, npages, nb, b.pages, (const uint32_t *)b.page_base,
-                       st.list);
+    const auto count = direct ? pages_count_kernel<false> : pages_count_kernel<true>;
+    const auto place = direct ? pages_place_kernel<false> : pages_place_kernel<true>;
+    hipLaunchKernelGGL(count, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, (const uint32_t *)st.tag, npages, nb, b.pages, b.elems, b.wg_off, stat, line_elems);
+    hipLaunchKernelGGL(pages_scan_kernel, dim3(1), dim3(1024), 0, stream, b.pages, b.elems, nb, b.page_base, b.slice_base, slice_pages, direct ? 1 : 0, scan_ctr);
+    hipLaunchKernelGGL(place, dim3(pgrid), dim3(PAGES_THREADS), 0, stream, st.tag, npages, nb, b.pages, (const uint32_t *)b.page_base, (const uint32_t *)b.wg_off, st.list);
+    if (hipPeekAtLastError() == hipSuccess) {
+        st.bkt_zero_nb = nb;
+        if (st.tags_dirty <= npages) st.tags_dirty = 0;
+    }
+    return 0;
 }
 
 // the histogram pass over sorted pages: a workgroup per slice of a bucket's list (bins16: two 16-bit counters per histogram word)
@@ -187,18 +217,21 @@ struct ScBatch {
     unsigned long long *d_table; DevCounters *d_ctr;
 };
 
-// sub-batch L through a scatter_bases_kernel pair into the pages of `st`; the tags and the bucket counts that the page sort starts from are cleared first
-// (region >= 0: into the L.npages pages of `st` that begin at page `region` -- the kernels number their pages from the pointers they are given --,
-//  and nothing is cleared: the deferred one-level path clears tags and bucket counts once per flush)
-inline int launch_bases(const BasesPair &kp, hipStream_t stream, ProfHook &prof, const ScatterState &st, int nb, const ScLaunch &L, int contig_pages,
+// sub-batch L through a scatter_bases_kernel pair into the pages of `st`, whose tags say "no page": the sort of the sub-batch before left them so,
+// and tags_clean sees to the rest
+// (region >= 0: into the L.npages pages of `st` that begin at page `region` -- the kernels number their pages from the pointers they are given --;
+//  the deferred one-level path looks after the tags itself, once per cycle)
+inline int launch_bases(const BasesPair &kp, hipStream_t stream, ProfHook &prof, ScatterState &st, const ScLaunch &L, int contig_pages,
                         const ScBatch &B, uint64_t t0, int ring_shift, int ring_bits, int sub_log2, int64_t region = -1)
 {
     ScOut out;
     out.pages = st.pages; out.tag = st.tag; out.extra_elems = L.extra_elems; out.wg_pages = L.wg_pages;
     out.wg_range = nullptr; out.contig = (uint32_t)contig_pages; out.wg_base = 0; out.grid = 0;
     if (region >= 0) { out.pages += (size_t)region * st.page_bytes; out.tag += (size_t)region; }
-    else if (hipMemsetAsync(st.tag, 0xFF, (size_t)L.npages * sizeof(uint32_t), stream) != hipSuccess ||
-             hipMemsetAsync(st.d_bkt, 0, 2 * (size_t)nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+    else {
+        if (tags_clean(st, stream)) return 1;
+        st.tags_dirty = L.npages;                                        // (until the sort has read them)
+    }
     prof.begin_on(KDB_KERNEL_SCATTER, stream);
     for (BasesKernel fn : kp.fn)
         hipLaunchKernelGGL(fn, dim3(L.G), dim3(kp.threads), 0, stream, B.d_bases, (uint64_t)B.nbytes, (uint32_t)t0, L.nt, B.k, ring_shift, ring_bits, sub_log2, out,
@@ -259,7 +292,7 @@ inline BasesPair select_one_level(const ScGeom &g, int k, int n_expand, int cano
 inline int scatter_stage1(ScatterState &st, const PagedOptions &opt, hipStream_t stream, const ScGeom &g, uint64_t t0, const ScBatch &B, ProfHook &prof, ScLaunch *L)
 {
     *L = sub_batch(g, t0, B.n_expand);
-    if (launch_bases(select_one_level(g, B.k, B.n_expand, B.canonical), stream, prof, st, g.nb, *L, opt.contig_pages, B, t0, g.lo_bits, g.nb_bits, g.sub_log2))
+    if (launch_bases(select_one_level(g, B.k, B.n_expand, B.canonical), stream, prof, st, *L, opt.contig_pages, B, t0, g.lo_bits, g.nb_bits, g.sub_log2))
         return 1;
     if (hipGetLastError() != hipSuccess) { partition_error_ref() = "paged scatter failed to launch"; return 1; }
     return 0;
@@ -272,8 +305,9 @@ inline int scatter_stage2(ScatterState &st, hipStream_t stream, const ScGeom &g,
     uint32_t slice_pages = (est_pages + target - 1) / target;
     if (slice_pages < 128u) slice_pages = 128u;                      // >= 64 Ki elements per histogram
     prof.begin_on(KDB_KERNEL_PAGE_SORT, stream);
-    page_sort(stream, st, L.npages, (uint32_t)g.nb, &B.d_ctr->pages_bases, 32u, slice_pages, 256u, B.d_ctr);
+    const int src = page_sort(stream, st, L.npages, (uint32_t)g.nb, &B.d_ctr->pages_bases, 32u, slice_pages, 256u, B.d_ctr);
     prof.end();
+    if (src) return src;
     prof.begin_on(KDB_KERNEL_PAGE_HIST, stream);
     hist_pass(stream, g.big, st, L.npages, (uint32_t)g.nb, slice_pages, B.d_table, g.lo_bits, g.hi_shift, 0, B.d_ctr);
     prof.end();
@@ -308,7 +342,6 @@ struct OneLevelPending {
     ScatterState arena;
     size_t used = 0;                       // pages of the regions handed out since the last flush: [0, used) is what the sort reads
     size_t est_pages = 0;                  // pages those batches are expected to have filled (sizes the pass's slices, as scatter_stage2 does for one batch)
-    size_t tags_dirty = 0;                 // tags [0, tags_dirty) may have been written since they were last cleared
     int pending = 0;                       // batches in the arena
     // what the pending batches were scattered under; a batch that differs in any of it flushes them first
     int k = 0, nb = 0, lo_bits = 0, hi_shift = 0; bool big = false;
@@ -321,10 +354,11 @@ constexpr size_t ARENA_BYTES_PER_PAGE = SC_PAGE_BYTES + sizeof(uint32_t) + sizeo
 
 inline void one_level_free(OneLevelPending &ol) { scatter_free(ol.arena); ol = OneLevelPending(); }
 
-// kdb_reset / after a flush: no batch is pending any more (the tags are cleared when the next cycle begins)
-inline void one_level_drop(OneLevelPending &ol)
+// kdb_reset / after a flush: no batch is pending any more.  A flush's sort has put the tags back to "no page"; tags that were written and are
+// dropped unsorted are cleared when the next cycle begins (arena.tags_dirty).
+inline void one_level_drop(OneLevelPending &ol, bool sorted = false)
 {
-    if (ol.used > ol.tags_dirty) ol.tags_dirty = ol.used;
+    if (!sorted && ol.used > ol.arena.tags_dirty) ol.arena.tags_dirty = ol.used;
     ol.used = 0; ol.est_pages = 0; ol.pending = 0;
 }
 
@@ -341,15 +375,15 @@ inline int one_level_flush(OneLevelPending &ol, hipStream_t stream, DevCounters 
     size_t slice_pages = (ol.est_pages + target - 1) / target;
     if (slice_pages < 128) slice_pages = 128;
     if (slice_pages > (1u << 17) - 1u) slice_pages = (1u << 17) - 1u;
-    if (hipMemsetAsync(ol.arena.d_bkt, 0, 2 * (size_t)ol.nb * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
     prof.begin_on(KDB_KERNEL_PAGE_SORT, stream);
-    page_sort(stream, ol.arena, (uint32_t)ol.used, (uint32_t)ol.nb, &d_ctr->pages_bases, 32u, (uint32_t)slice_pages, 256u, d_ctr);
+    const int src = page_sort(stream, ol.arena, (uint32_t)ol.used, (uint32_t)ol.nb, &d_ctr->pages_bases, 32u, (uint32_t)slice_pages, 256u, d_ctr);
     prof.end();
+    if (src) return src;
     prof.begin_on(KDB_KERNEL_PAGE_HIST, stream);
     hist_pass(stream, ol.big, ol.arena, (uint32_t)ol.used, (uint32_t)ol.nb, (uint32_t)slice_pages, ol.d_table, ol.lo_bits, ol.hi_shift, 0, d_ctr);
     prof.end();
     ol.flushes++; ol.flushed_batches += (uint64_t)ol.pending;
-    one_level_drop(ol);
+    one_level_drop(ol, ol.arena.tags_dirty == 0);
     if (hipGetLastError() != hipSuccess) { partition_error_ref() = "histogram pass over the one-level arena failed to launch"; return 1; }
     return 0;
 }
@@ -385,22 +419,15 @@ inline int one_level_room(OneLevelPending &ol, const PagedOptions &opt, hipStrea
         ol.reallocs++;
         if (page_set_alloc(ol.arena, want, SC_PAGE_BYTES) != 0) {
             ol.grow_failed = true;                                      // (what could be had is the budget from now on)
-            if (page_set_alloc(ol.arena, 2 * need, SC_PAGE_BYTES) != 0) { ol.tags_dirty = 0; return 3; }
+            if (page_set_alloc(ol.arena, 2 * need, SC_PAGE_BYTES) != 0) return 3;
         }
-        ol.tags_dirty = ol.arena.cap;
     }
     const int rc = bkt_reserve(ol.arena, stream, nb);
     return rc == 2 ? 3 : rc;
 }
 
-// the tags a cycle begins with say "no page"
-inline int one_level_begin_cycle(OneLevelPending &ol, hipStream_t stream)
-{
-    if (ol.tags_dirty > ol.arena.cap) ol.tags_dirty = ol.arena.cap;
-    if (ol.tags_dirty && hipMemsetAsync(ol.arena.tag, 0xFF, ol.tags_dirty * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
-    ol.tags_dirty = 0;
-    return 0;
-}
+// the tags a cycle begins with say "no page": after a flush they do, and nothing is cleared
+inline int one_level_begin_cycle(OneLevelPending &ol, hipStream_t stream) { return tags_clean(ol.arena, stream); }
 
 // returns 0 ok (the batch is scattered; its counts reach the vector with the next flush), 1 error (partition_error()),
 // 3 no room for an arena of two regions (nothing of the batch was counted and nothing is pending): count it with scatter_count
@@ -419,7 +446,7 @@ inline int scatter_count_deferred(OneLevelPending &ol, const PagedOptions &opt, 
         // (a later sub-batch of a batch of more than 2 Gi positions: the arena holds two of the largest, so after a flush it fits)
         if (ol.used + L.npages > ol.arena.cap) { ol.full_flushes++; if (one_level_flush(ol, stream, B.d_ctr, prof)) return 1; }
         if (ol.used == 0 && one_level_begin_cycle(ol, stream)) return 1;
-        if (launch_bases(kp, stream, prof, ol.arena, g.nb, L, opt.contig_pages, B, t0, g.lo_bits, g.nb_bits, g.sub_log2, (int64_t)ol.used)) return 1;
+        if (launch_bases(kp, stream, prof, ol.arena, L, opt.contig_pages, B, t0, g.lo_bits, g.nb_bits, g.sub_log2, (int64_t)ol.used)) return 1;
         if (hipGetLastError() != hipSuccess) { partition_error_ref() = "paged scatter failed to launch"; return 1; }
         ol.used += L.npages;
         ol.est_pages += one_level_est_pages(g, L);
@@ -537,7 +564,6 @@ struct TwoLevelPaged {
     bool probe_live[PROBES] = {false};
     int probe_next = 0;
     size_t slack = 0;                      // used2 - slack = the host's present bound on the cursor
-    size_t tags_dirty = 0;                 // arena tags [0, tags_dirty) may have been written since they were last cleared
     int pending = 0;                       // batches in the arena
     int k_pending = 0;
     size_t budget_decided = 0;             // the arena's size where the option leaves it open (PagedOptions::budget_bytes = 0): decided at first use
@@ -561,10 +587,11 @@ inline void twolevel_paged_free(TwoLevelPaged &tp)
     tp = TwoLevelPaged();
 }
 
-// kdb_reset / after a flush: no batch is pending any more (the cursor and the tags are cleared when the next cycle begins)
-inline void twolevel_paged_drop(TwoLevelPaged &tp)
+// kdb_reset / after a flush: no batch is pending any more (the cursor is cleared when the next cycle begins; so are the tags, unless
+// the flush's sort has read them all and so put them back to "no page")
+inline void twolevel_paged_drop(TwoLevelPaged &tp, bool sorted = false)
 {
-    if (tp.used2 - tp.slack > tp.tags_dirty) tp.tags_dirty = tp.used2 - tp.slack;
+    if (!sorted && tp.used2 - tp.slack > tp.arena.tags_dirty) tp.arena.tags_dirty = tp.used2 - tp.slack;
     tp.used2 = 0; tp.slack = 0; tp.pending = 0;
     for (int i = 0; i < TwoLevelPaged::PROBES; i++) tp.probe_live[i] = false;
 }
@@ -628,18 +655,18 @@ inline int twolevel_paged_flush(TwoLevelPaged &tp, const PagedOptions &opt, hipS
     // npages = 0: the device's cursor has told the host that the pending batches took no page at all (not one countable window among them: reads of
     // N's in drop mode): nothing to sort, nothing to add -- and a launch with an empty grid is an error (found by tests/fuzz_gpu.py, round 4)
     if (npages != 0) {
-        if (hipMemsetAsync(tp.arena.d_bkt, 0, 2 * (size_t)g.nb2 * sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
         uint32_t slice_pages = (npages + 2047u) / 2048u;
         if (slice_pages < 128u) slice_pages = 128u;
         prof.begin_on(KDB_KERNEL_PAGE_SORT, stream);
-        page_sort(stream, tp.arena, npages, g.nb2, &d_ctr->pages_ids, 32u, slice_pages, 2048u /* (small chunks: few leading digits per LDS window) */, nullptr);
+        const int src = page_sort(stream, tp.arena, npages, g.nb2, &d_ctr->pages_ids, 32u, slice_pages, 2048u /* (small chunks: few leading digits per LDS window) */, nullptr);
         prof.end();
+        if (src) return src;
         prof.begin_on(KDB_KERNEL_PAGE_HIST, stream);
         hist_pass(stream, g.wide, tp.arena, npages, g.nb2, slice_pages, d_table, g.lo_bits, g.lo_bits + g.d1 + 9, table_is_zero, d_ctr);
         prof.end();
     }
     tp.flushes++; tp.flushed_batches += (uint64_t)tp.pending;
-    twolevel_paged_drop(tp);
+    twolevel_paged_drop(tp, tp.arena.tags_dirty == 0);                  // (npages = 0: no tag was written)
     if (hipGetLastError() != hipSuccess) { partition_error_ref() = "histogram pass over the page arena failed to launch"; return 1; }
     return 0;
 }
@@ -668,7 +695,7 @@ inline int arena_allocate(TwoLevelPaged &tp, hipStream_t stream, size_t want_cap
     const size_t tries[3] = {want_cap, old_cap >= need2 ? old_cap : need2, need2};
     for (int attempt = 0; attempt < 3 && !tp.arena.pages; attempt++) {
         if (attempt && tries[attempt] == tries[attempt - 1]) continue;
-        if (page_set_alloc(tp.arena, tries[attempt], SC_PAGE_BYTES) == 0) { tp.tags_dirty = tp.arena.cap; if (attempt) tp.grow_failed = true; }
+        if (page_set_alloc(tp.arena, tries[attempt], SC_PAGE_BYTES) == 0 && attempt) tp.grow_failed = true;
     }
     tp.reallocs++;
     tp.full_flushes = 0;
@@ -725,10 +752,8 @@ inline int arena_room(TwoLevelPaged &tp, const PagedOptions &opt, hipStream_t st
     }
     if (tp.pending == 0) {
         // a new cycle: the cursor goes back to the start of the arena, and the tags the last cycle (or a fresh allocation) left behind are cleared
-        if (tp.tags_dirty > tp.arena.cap) tp.tags_dirty = tp.arena.cap;
-        if (hipMemsetAsync(tp.d_cursor, 0, sizeof(uint32_t), stream) != hipSuccess ||
-            (tp.tags_dirty && hipMemsetAsync(tp.arena.tag, 0xFF, tp.tags_dirty * sizeof(uint32_t), stream) != hipSuccess)) { partition_error_ref() = "memset failed"; return 1; }
-        tp.tags_dirty = 0;
+        if (hipMemsetAsync(tp.d_cursor, 0, sizeof(uint32_t), stream) != hipSuccess) { partition_error_ref() = "memset failed"; return 1; }
+        if (tags_clean(tp.arena, stream)) return 1;
     }
     return 0;
 }
@@ -774,10 +799,10 @@ inline IdsKernel select_level2(const L1Geom &g, const PagedOptions &opt)
 inline int twolevel_level1(TwoLevelPaged &tp, const PagedOptions &opt, hipStream_t stream, const L1Geom &g, const ScLaunch &L, uint64_t t0, size_t need2, const ScBatch &B,
                            ProfHook &prof)
 {
-    if (launch_bases(select_level1(g, opt, B.k, B.n_expand, B.canonical), stream, prof, tp.l1, g.nb1, L, opt.contig_pages, B, t0, g.lo_bits + 9, g.d1, g.sub_log2))
+    if (launch_bases(select_level1(g, opt, B.k, B.n_expand, B.canonical), stream, prof, tp.l1, L, opt.contig_pages, B, t0, g.lo_bits + 9, g.d1, g.sub_log2))
         return 1;
     prof.begin_on(KDB_KERNEL_PAGE_SORT, stream);
-    page_sort(stream, tp.l1, L.npages, (uint32_t)g.nb1, &B.d_ctr->pages_bases, g.wide ? 16u : 32u, 1u << 20, 256u, B.d_ctr);
+    if (page_sort(stream, tp.l1, L.npages, (uint32_t)g.nb1, &B.d_ctr->pages_bases, g.wide ? 16u : 32u, 1u << 20, 256u, B.d_ctr)) { prof.end(); return 1; }
     hipLaunchKernelGGL(l2_plan_kernel, dim3(1), dim3(1024), 0, stream, (const uint32_t *)bkt_arrays(tp.l1, (size_t)g.nb1).page_base, (uint32_t)g.nb1, g.G2, 512u, g.page_elems, tp.d_wg_range, tp.d_cursor,
                        (uint32_t)tp.arena.cap, B.d_ctr);
     prof.end();
