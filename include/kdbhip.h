@@ -391,6 +391,43 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
                     double *kernel_ms_out /* may be NULL */);
 
 /*
+ * One small k-mer table per record (csrc/kdb_tables.hip.h): what the reference's codon tables are made of
+ * (kmerdb/codons.py:175-333: k = 3, stride = 3, canonical ids) and, with stride 1, the composition vector of every record.
+ * Record r holds the residues bases[off[r] .. off[r + 1]), len of them.  Its windows start at p_i = phase_r + i stride for every i >= 0
+ * with p_i + k <= len; phase_r is 0, but for record 0 under KDB_TABLES_CONTINUES it is `phase`.  A window is COUNTED if its k residues
+ * are all of A, C, G, T and SKIPPED if it holds an N (the frame is kept: codons.py:205-215).
+ *   tables_out[r][id] = the number of counted windows with that id; id = the forward id, with canonical != 0 min(id, rc(id)), rc as in
+ *                       kdb_strand_merge.  A row is 4^k entries wide either way.
+ *   windows_out[r]    = the number of counted windows
+ *   skipped_out[r]    = the number of skipped windows
+ *   first_id_out[r] / last_id_out[r] = the id of the counted window with the smallest / largest p, -1 without one
+ * All five are exact integers and do not depend on the grid, on the other records of the batch or on the record's place among them.
+ * A record shorter than k, an empty one included, is no error: a row of zeros, 0, 0, -1, -1.
+ * bases / read_offsets and all outputs: host memory.  Synchronous; scratch is allocated and freed inside the call.
+ * KDB_TABLES_CONTINUES: record 0 is the next piece of the previous call's last record and begins with the last k - 1 residues already
+ * given; phase (0 <= phase < stride) is where its first window starts, so that the record's windows keep their frame.  The caller works
+ * it out (the length and first phase of the piece before fix where the next window of the record starts) and joins the pieces: rows and
+ * counts added, the first first_id that is not -1, the last last_id that is not -1.
+ * KDB_ERR_ARG, all settled on the host before anything is launched: k outside 1..6 (4^6 uint32 are the 16 KiB of LDS one wave owns),
+ * stride outside 1..k, phase >= stride, phase != 0 without the flag, unknown flags, a NULL buffer, offsets that do not start at 0, end at
+ * nbytes and rise, more than 2^30 residues or records, nreads 4^k above 2^31 table entries, residues but no records.  No records and no
+ * residues: KDB_OK.
+ * KDB_ERR_BAD_RESIDUE: a byte outside upper-case ACGTN anywhere in the batch; the outputs are then not written.  This is one step
+ * stricter than the reference, which never looks at the letters of a triplet that holds an N (codons.py:205-215) and so lets an IUPAC
+ * letter beside an N pass.
+ * KDB_ERR_NOMEM: the scratch does not fit.  kernel_ms_out (may be NULL): device time of the kernels, by HIP events.
+ * KDB_TABLES_PIECE: windows one wave counts; a record of more windows is cut into pieces of that many, whose rows are added.
+ */
+#define KDB_TABLES_CONTINUES 1
+#define KDB_TABLES_PIECE 8192
+#define KDB_TABLES_MAX_K 6
+int kdb_record_tables(int device_id, int k, int stride, int canonical, uint64_t phase,
+                      const uint8_t *bases, size_t nbytes, const uint64_t *read_offsets, size_t nreads, int flags,
+                      uint32_t *tables_out /* nreads x 4^k, row-major */,
+                      uint64_t *windows_out, uint64_t *skipped_out, int32_t *first_id_out, int32_t *last_id_out /* nreads each */,
+                      double *kernel_ms_out /* may be NULL */);
+
+/*
  * Host-side record splitter (no GPU work): what Bio.SeqIO.parse does for kmerdb/parse.py:50-85 on this path.
  * FASTQ: parses whole records of text[0, n) into bases_out (concatenated residues) and offsets_out
  * (nreads+1 entries); *consumed_out = bytes of text used (stops before a trailing partial record unless at_eof).

@@ -24,6 +24,7 @@ KDB_PAIRSTATS_BLOCK, KDB_PAIRSTATS_HALF, KDB_PAIRSTATS_WG_BINS = 4, 2, 512
 KDB_PAIRFLOAT_GRID_MAX = 512
 KDB_SIZEFACTORS_WG_BINS, KDB_SIZEFACTORS_GRID_MAX = 512, 1024
 KDB_SCORE_CONTINUES, KDB_SCORE_PIECE, KDB_SCORE_LANES = 1, 2048, 64
+KDB_TABLES_CONTINUES, KDB_TABLES_PIECE, KDB_TABLES_MAX_K = 1, 8192, 6
 ABI_VERSION = 6
 
 # every symbol include/kdbhip.h declares: (name, restype, argtypes)
@@ -71,7 +72,9 @@ SYMBOLS = (
     ("kdb_window_ids", ctypes.c_int, [_vp, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp]),
     ("kdb_score_reads", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
                                        ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double)]),
-    ("kdb_parse_fastq", ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp,
+    ("kdb_record_tables", ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint64, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t,
+                                         ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_parse_fastq",ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp,
                                        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     ("kdb_parse_fastq_mt", ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp,
                                           ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.c_int]),

@@ -1,7 +1,7 @@
 // kdb_analysis_host.hip.h -- host side of the analysis calls of include/kdbhip.h, the ones that take finished vectors and no kdb_engine:
-// kdb_gram, kdb_pairstats, kdb_pairfloat, kdb_size_factors, kdb_scale_counts, kdb_spectrum, kdb_rank_transform, kdb_strand_merge and
-// kdb_score_reads.  Every call works in an AnalysisCall: its own stream, events and scratch, gone when it returns.  What the host alone
-// decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.
+// kdb_gram, kdb_pairstats, kdb_pairfloat, kdb_size_factors, kdb_scale_counts, kdb_spectrum, kdb_rank_transform, kdb_strand_merge,
+// kdb_score_reads and kdb_record_tables (which takes residues alone).  Every call works in an AnalysisCall: its own stream, events and
+// scratch, gone when it returns.  What the host alone decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +23,7 @@
 #include "kdb_spectrum_host.cpp.h"
 #include "kdb_strands.hip.h"
 #include "kdb_score.hip.h"
+#include "kdb_tables.hip.h"
 #include "kdb_sweep_plan.cpp.h"
 
 namespace {
@@ -615,6 +616,83 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
     HIP_TRY(hipMemcpy(windows_out, ints, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(zero_windows_out, ints + nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(min_count_out, ints + 2 * nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return KDB_OK;
+}
+
+// ---- one k-mer table per record (kdb_tables.hip.h) ----
+int kdb_record_tables(int device_id, int k, int stride, int canonical, uint64_t phase, const uint8_t *bases, size_t nbytes, const uint64_t *offs, size_t nreads,
+                      int flags, uint32_t *tables_out, uint64_t *windows_out, uint64_t *skipped_out, int32_t *first_id_out, int32_t *last_id_out,
+                      double *kernel_ms_out)
+{
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (k < 1 || k > kdbtables::MAX_K) return fail(KDB_ERR_ARG, "kdb_record_tables: k=%d out of range 1..%d", k, kdbtables::MAX_K);
+    if (stride < 1 || stride > k) return fail(KDB_ERR_ARG, "kdb_record_tables: stride=%d out of range 1..k=%d", stride, k);
+    if (flags & ~KDB_TABLES_CONTINUES) return fail(KDB_ERR_ARG, "kdb_record_tables: unknown flags %d", flags);
+    const bool continues = (flags & KDB_TABLES_CONTINUES) != 0;
+    if (phase >= (uint64_t)stride) return fail(KDB_ERR_ARG, "kdb_record_tables: phase=%llu must be below stride=%d", (unsigned long long)phase, stride);
+    if (phase != 0 && !continues) return fail(KDB_ERR_ARG, "kdb_record_tables: a phase needs KDB_TABLES_CONTINUES");
+    if (nreads == 0) return nbytes == 0 ? KDB_OK : fail(KDB_ERR_ARG, "kdb_record_tables: residues but no records");
+    if (!offs || (!bases && nbytes) || !tables_out || !windows_out || !skipped_out || !first_id_out || !last_id_out)
+        return fail(KDB_ERR_ARG, "kdb_record_tables: NULL buffer");
+    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_record_tables: at most 2^30 residues per call");
+    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_record_tables: at most 2^30 records per call");
+    // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
+    kdbplan::TablesLayout lay;
+    if (const kdbplan::LayoutError bad = kdbplan::tables_layout(offs, nreads, nbytes, k, stride, phase, kdbtables::PIECE, 1ull << 31, lay))
+        return fail(KDB_ERR_ARG, bad == kdbplan::LAYOUT_ENTRIES ? "kdb_record_tables: more than 2^31 table entries (records x 4^k) in one call"
+                                 : bad == kdbplan::LAYOUT_ENDS  ? "read_offsets must start at 0 and end at nbytes"
+                                                                : "read_offsets must rise from 0 to nbytes");
+    // so are the residues: every byte is one of ACGTN, or nothing is launched
+    // (a block at a time into one byte, which the compiler keeps in byte lanes: 4-5 x the rate of counting into 64 bits; a block is
+    // counted only where it holds an offender)
+    uint64_t nbad = 0;
+    auto outside = [](uint8_t b) { return !((b == 'A') | (b == 'C') | (b == 'G') | (b == 'T') | (b == 'N')); };
+    for (size_t at = 0; at < nbytes; at += 4096) {
+        const size_t n = std::min<size_t>(4096, nbytes - at);
+        uint8_t any = 0;
+        for (size_t i = 0; i < n; i++) any |= (uint8_t)outside(bases[at + i]);
+        if (any) for (size_t i = 0; i < n; i++) nbad += outside(bases[at + i]);
+    }
+    if (nbad) return fail(KDB_ERR_BAD_RESIDUE, "kdb_record_tables: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
+    const uint64_t npieces = lay.npieces, nbins = 1ull << (2 * k), nmulti = lay.multi.size();
+    AnalysisCall call;
+    if (int rc = call.open(device_id)) return rc;
+
+    auto *d_bases = call.alloc<uint8_t>(((nbytes + 15) & ~(size_t)15) + 32);           // (tables_piece_kernel's aligned words reach 15 bytes past a window's start)
+    auto *d_offs = call.alloc<uint64_t>(nreads + 1);
+    auto *rec_piece0 = call.alloc<uint32_t>(nreads + 1), *piece_rec = nmulti ? call.alloc<uint32_t>(npieces) : nullptr;
+    auto *multi = nmulti ? call.alloc<uint32_t>(nmulti) : nullptr;
+    auto *pieces = call.alloc<kdbtables::PieceOut>(npieces);
+    auto *tables = call.alloc<uint32_t>(nreads * nbins);
+    auto *counts = call.alloc<unsigned long long>(2 * nreads);
+    auto *ends = call.alloc<int32_t>(2 * nreads);
+    if (!d_bases || !d_offs || !rec_piece0 || (nmulti && (!piece_rec || !multi)) || !pieces || !tables || !counts || !ends)
+        return fail(KDB_ERR_NOMEM, "kdb_record_tables: no room for the scratch of %zu residues in %zu records of 4^%d entries", nbytes, nreads, k);
+    if (nbytes) HIP_TRY(hipMemcpyAsync(d_bases, bases, nbytes, hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(rec_piece0, lay.rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    if (nmulti) {
+        HIP_TRY(hipMemcpyAsync(piece_rec, lay.piece_rec.data(), npieces * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(multi, lay.multi.data(), nmulti * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    }
+    HIP_TRY(call.begin());
+    if (nmulti)
+        hipLaunchKernelGGL(kdbtables::tables_zero_kernel, dim3((unsigned)std::min<uint64_t>(nmulti, 4096)), dim3(256), 0, call.st, (const uint32_t *)multi,
+                           (uint32_t)nmulti, k, tables);
+    hipLaunchKernelGGL(kdbtables::tables_piece_kernel, dim3((unsigned)((npieces + kdbtables::WAVES - 1) / kdbtables::WAVES)), dim3(kdbtables::TPB),
+                       kdbtables::lds_bytes(k), call.st, (const uint8_t *)d_bases, (const uint64_t *)d_offs, (const uint32_t *)piece_rec,
+                       (const uint32_t *)rec_piece0, (uint32_t)npieces, k, stride, canonical ? 1 : 0, (uint32_t)phase, tables, pieces);
+    hipLaunchKernelGGL(kdbtables::tables_record_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, call.st, (const kdbtables::PieceOut *)pieces,
+                       (const uint32_t *)rec_piece0, (uint64_t)nreads, counts, counts + nreads, ends, ends + nreads);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(call.end());
+    HIP_TRY(hipMemcpyAsync(tables_out, tables, nreads * nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(windows_out, counts, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(skipped_out, counts + nreads, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(first_id_out, ends, nreads * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(last_id_out, ends + nreads, nreads * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    HIP_TRY(call.elapsed(kernel_ms_out));
     return KDB_OK;
 }
 

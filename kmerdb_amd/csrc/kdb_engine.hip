@@ -28,6 +28,7 @@
 #include "kdb_spectrum.hip.h"
 #include "kdb_strands.hip.h"
 #include "kdb_score.hip.h"
+#include "kdb_tables.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
 

@@ -1,7 +1,7 @@
 // kdb_sweep_plan.cpp.h -- the host-only plans of the analysis calls (plain C++, no HIP: tests/c/sweep_plan_check.cpp compiles it alone, runs
 // it under the sanitizers and prints the plans for tests/sweep_cases.py to be compared with): which block pairs become which launch rows,
 // in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, and how the records of
-// kdb_score_reads split into pieces.  The block size, HALF, the chunk sizes and the piece size are arguments: the kernel headers have them.
+// kdb_score_reads and of kdb_record_tables (tests/c/tables_plan_check.cpp) split into pieces.  The block size, HALF, the chunk sizes and the piece size are arguments: the kernel headers have them.
 // A row type is the kernel header's (kdbgram::Row, kdbpair::Row, kdbpair::FloatRow) or any struct of as many uint8_t fields.
 #pragma once
 #include <cstdint>
@@ -94,7 +94,8 @@ inline uint32_t rows_cap(uint32_t nrows, uint32_t many_rows, uint32_t cap, uint3
 // without a window has an empty one); piece_rec[p] = the record of piece p, left empty when every record is one piece.  offs: nreads + 1
 // offsets into nbytes residues, nreads >= 1.  A record shorter than k counts as short unless it is the first and `continues` an earlier
 // call's; where there are short records piece_rec is left empty too: the caller refuses them.
-enum LayoutError { LAYOUT_OK = 0, LAYOUT_ENDS /* must start at 0 and end at nbytes */, LAYOUT_RISE /* must rise from 0 to nbytes */ };
+enum LayoutError { LAYOUT_OK = 0, LAYOUT_ENDS /* must start at 0 and end at nbytes */, LAYOUT_RISE /* must rise from 0 to nbytes */,
+                   LAYOUT_ENTRIES /* kdb_record_tables: more table entries than the call allows */ };
 
 struct ScoreLayout {
     std::vector<uint32_t> rec_piece0, piece_rec;
@@ -116,6 +117,54 @@ inline LayoutError score_layout(const uint64_t *offs, size_t nreads, uint64_t nb
     }
     lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
     if (lay.nshort == 0 && lay.npieces != nreads) {
+        lay.piece_rec.resize(lay.npieces);
+        for (size_t r = 0; r < nreads; r++)
+            for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
+    }
+    return LAYOUT_OK;
+}
+
+// kdb_record_tables: the windows of a record of len residues start at phase + i stride, for every i with phase + i stride + k <= len
+// (constexpr: the kernel counts them with the same expression)
+constexpr uint64_t tables_windows(uint64_t len, int k, int stride, uint64_t phase)
+{
+    return len >= (uint64_t)k + phase ? (len - (uint64_t)k - phase) / (uint64_t)stride + 1 : 0;
+}
+
+// Record r is pieces rec_piece0[r] .. rec_piece0[r + 1] of at most `piece` windows each and at least one (a record without a window has an
+// empty one): piece p of it holds the windows (p - rec_piece0[r]) piece .. of the record's tables_windows(), `phase` for record 0 and 0 for
+// the others.  piece_rec[p] = the record of piece p, left empty when every record is one piece.  multi: the records of more than one
+// piece, in order -- their rows are added to by several waves and are zeroed first; every other row is stored whole by its only wave.
+// LAYOUT_ENTRIES: nreads 4^k is above max_entries.
+struct TablesLayout {
+    std::vector<uint32_t> rec_piece0, piece_rec, multi;
+    uint64_t npieces = 0;
+    // the windows [first, first + count) of piece p of record r, which has nwin of them
+    static void piece_windows(uint64_t nwin, uint32_t p_in_rec, uint32_t piece, uint64_t &first, uint32_t &count)
+    {
+        first = (uint64_t)p_in_rec * piece;
+        count = (uint32_t)std::min<uint64_t>(piece, nwin > first ? nwin - first : 0);
+    }
+};
+
+inline LayoutError tables_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, int k, int stride, uint64_t phase, uint32_t piece, uint64_t max_entries,
+                                 TablesLayout &lay)
+{
+    lay = TablesLayout();
+    if (offs[0] != 0 || offs[nreads] != nbytes) return LAYOUT_ENDS;
+    for (size_t r = 0; r < nreads; r++)
+        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
+    if ((uint64_t)nreads > (max_entries >> (2 * k))) return LAYOUT_ENTRIES;
+    lay.rec_piece0.resize(nreads + 1);
+    for (size_t r = 0; r < nreads; r++) {
+        const uint64_t nwin = tables_windows(offs[r + 1] - offs[r], k, stride, r == 0 ? phase : 0);
+        const uint64_t n = std::max<uint64_t>(1, (nwin + piece - 1) / piece);
+        lay.rec_piece0[r] = (uint32_t)lay.npieces;
+        lay.npieces += n;                                                         // (< 2^31: 2^30 records and 2^30 windows at most)
+        if (n > 1) lay.multi.push_back((uint32_t)r);
+    }
+    lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
+    if (!lay.multi.empty()) {
         lay.piece_rec.resize(lay.npieces);
         for (size_t r = 0; r < nreads; r++)
             for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;

@@ -233,15 +233,61 @@ def build_parser():
     rp.add_argument("--device", type=int, default=0)
     rp.add_argument("seqfile", help="sequences to score, .fasta or .fastq (optionally gzipped)")
     rp.add_argument("kdb", help="the k-mer profile (.kdb)")
+    cp = sub.add_parser("composition", help="k-mer composition of every record of a FASTA/FASTQ file: one line of 4^k counts per record")
+    cp.add_argument("-k", type=int, required=True, help="1..6")
+    cp.add_argument("--do-not-canonicalize", action="store_true", help="all 4^k forward columns, not the columns with id <= rc(id)")
+    cp.add_argument("--as-frequencies", action="store_true", help="count / windows instead of counts")
+    cp.add_argument("--output-delimiter", default="\t")
+    cp.add_argument("--device", type=int, default=0)
+    cp.add_argument("seqfile", help=".fasta or .fastq (optionally gzipped)")
+    kp = sub.add_parser("codons", help="codon counts of every CDS of a FASTA file (__init__.py:214-299)")
+    kp.add_argument("--as-frequencies", action="store_true", help="frequencies inside the synonymous families instead of counts")
+    kp.add_argument("--ignore-invalid-cds", action="store_true", help="leave out sequences whose length is not divisible by 3")
+    kp.add_argument("--include-noncanonicals", action="store_true", help="keep sequences with an unusual start or stop codon, or an N")
+    kp.add_argument("--include-stop-codons", action="store_true")
+    kp.add_argument("--include-start-codons", action="store_true")
+    kp.add_argument("--no-stop-codons-in-table", action="store_true", help="print the 61 columns that are no stop codon")
+    kp.add_argument("--output-delimiter", default="\t")
+    kp.add_argument("--as-reference", action="store_true", help="the reference's ids (min of both strands) and serine family, bit for bit")
+    kp.add_argument("--device", type=int, default=0)
+    kp.add_argument("fasta")
+    up = sub.add_parser("CUB", help="chi-square of every gene's codon usage against a `codons` table (__init__.py:302-421)")
+    up.add_argument("--sequences", required=True, help="the genes to test, FASTA")
+    up.add_argument("--delimiter", default="\t", help="of the input table")
+    up.add_argument("--output-delimiter", default="\t")
+    up.add_argument("--include-stop-codons", action="store_true")
+    up.add_argument("--include-start-codons", action="store_true")
+    up.add_argument("--ignore-invalid-cds", action="store_true")
+    up.add_argument("--ddof", type=int, default=60, help="delta degrees of freedom: 60, the reference's, leaves none and the p-value is nan")
+    up.add_argument("--as-reference", action="store_true")
+    up.add_argument("--device", type=int, default=0)
+    up.add_argument("input", help="a table as `codons` prints it, 64 or 61 columns")
     return ap
 
 
 def main(argv=None):
     """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
     `graph`, `distance <metric> a.kdb b.kdb ...`, `matrix <method> a.kdb b.kdb ...`, `spectrum a.kdb ...` and
-    `probability <seqfile> <kdb>` beside it."""
+    `probability <seqfile> <kdb>` beside it; `composition -k K seqfile`, `codons fasta` and `CUB --sequences fasta table` count per record."""
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.cmd == "composition":
+        from . import composition
+        composition.composition(a.seqfile, a.k, canonical=not a.do_not_canonicalize, as_frequencies=a.as_frequencies,
+                                output_delimiter=a.output_delimiter, device=a.device)
+        return 0
+    if a.cmd == "codons":
+        from . import codons
+        codons.codons(a.fasta, as_frequencies=a.as_frequencies, ignore_invalid_cds=a.ignore_invalid_cds, include_noncanonicals=a.include_noncanonicals,
+                      include_stop_codons=a.include_stop_codons, include_start_codons=a.include_start_codons,
+                      no_stop_codons_in_table=a.no_stop_codons_in_table, output_delimiter=a.output_delimiter, as_reference=a.as_reference, device=a.device)
+        return 0
+    if a.cmd == "CUB":
+        from . import codons
+        codons.codon_usage_bias(a.input, a.sequences, delimiter=a.delimiter, output_delimiter=a.output_delimiter,
+                                include_start_codons=a.include_start_codons, include_stop_codons=a.include_stop_codons,
+                                ignore_invalid_cds=a.ignore_invalid_cds, ddof=a.ddof, as_reference=a.as_reference, device=a.device)
+        return 0
     if a.cmd == "probability":
         from . import probability
         probability.probabilities(a.seqfile, a.kdb, pseudocount=a.pseudocount, output_delimiter=a.output_delimiter, device=a.device)
