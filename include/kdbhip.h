@@ -428,6 +428,51 @@ int kdb_record_tables(int device_id, int k, int stride, int canonical, uint64_t 
                       double *kernel_ms_out /* may be NULL */);
 
 /*
+ * The (w,k)-minimizers of every record (csrc/kdb_minimizers.hip.h): the sketch that read mappers, containment
+ * estimates and index subsampling start from.  The reference's `minimizers` subcommand (kmerdb/minimizer.py) flags every window_size-th
+ * of 4^k - k + 1 positions, which is no minimizer scheme; this call computes the usual one.
+ * Record r holds the residues bases[off[r] .. off[r + 1]), len of them.  Its start positions are 0 .. nwin - 1 with nwin = len - k + 1
+ * (0 if len < k).  Position p has an id iff kdb_window_ids of a forward ids-engine emits one for it (the window lies whole inside the
+ * record and every residue is one of A, C, G, T); fwd(p) is that id, rc as in kdb_strand_merge, and
+ *   id(p)     = canonical ? min(fwd, rc(fwd)) : fwd
+ *   strand(p) = 1 iff canonical and rc(fwd) < fwd, else 0
+ *   key(p)    = id(p) under KDB_MINIMIZER_LEX; under KDB_MINIMIZER_HASHED h(id(p)) with m = 4^k - 1 and every step masked:
+ *                 x = (~x + (x << 21)) & m;  x ^= x >> 24;  x = (x + (x << 3) + (x << 8)) & m;  x ^= x >> 14;
+ *                 x = (x + (x << 2) + (x << 4)) & m;  x ^= x >> 28;  x = (x + (x << 31)) & m;
+ *               (a bijection of [0, 4^k): equal keys mean equal ids).  A position without an id has key +infinity.
+ * With we = min(w, nwin): for every run of we consecutive start positions s .. s + we - 1, 0 <= s <= nwin - we, whose smallest key is
+ * finite, the LEFTMOST position holding that key is selected.  A record's minimizers are its selected positions, each once, ascending.
+ * A record with 1 <= nwin < w is one run; one with nwin = 0 or no finite key has none, which is no error.
+ *   counts_out[r] = the number of minimizers of record r; S_r = counts_out[0] + .. + counts_out[r - 1]
+ *   ids_out / pos_out / strand_out [S_r .. S_r + counts_out[r]) = id(p), p and strand(p) of record r's minimizers, by position
+ *   *total_out    = the sum of the counts
+ * All are exact integers and do not depend on the grid, on the other records of the batch or on the record's place among them.
+ * counts_out and *total_out are written whenever the status is KDB_OK.  The flat arrays hold `cap` entries and are written only if
+ * *total_out <= cap; otherwise they are left as they were and the status is still KDB_OK: the caller compares and calls again with room.
+ * cap == 0 with NULL flat pointers asks for the sizes alone.  strand_out may be NULL whatever cap is.
+ * bases / read_offsets and all outputs: host memory.  Synchronous; scratch is allocated and freed inside the call.
+ * KDB_ERR_ARG, all settled on the host before anything is launched: k outside 1..KDB_MINIMIZER_MAX_K (keys and ids in 64 bits), w outside
+ * 1..KDB_MINIMIZER_MAX_W, an order that is neither of the two, NULL counts_out, total_out or offsets, NULL ids_out or pos_out with
+ * cap > 0, offsets that do not start at 0, end at nbytes and rise, more than 2^30 residues or records, residues but no records.  No
+ * records and no residues: KDB_OK, *total_out = 0.
+ * KDB_ERR_BAD_RESIDUE: a byte outside upper-case ACGTN anywhere in the batch; no output is written (as kdb_record_tables).
+ * KDB_ERR_NOMEM: the scratch does not fit.  kernel_ms_out (may be NULL): device time of the kernels, by HIP events.
+ * KDB_MINIMIZER_PIECE: start positions one wave owns; a record of more is cut into pieces of that many, each of which reads the keys of
+ * w - 1 positions on either side and so decides its own positions alone.
+ */
+#define KDB_MINIMIZER_LEX     0
+#define KDB_MINIMIZER_HASHED  1
+#define KDB_MINIMIZER_MAX_K   31
+#define KDB_MINIMIZER_MAX_W   256
+#define KDB_MINIMIZER_PIECE   2048
+int kdb_minimizers(int device_id, int k, int w, int canonical, int order,
+                   const uint8_t *bases, size_t nbytes, const uint64_t *read_offsets, size_t nreads,
+                   uint64_t *counts_out /* nreads */,
+                   uint64_t *ids_out, uint32_t *pos_out, uint8_t *strand_out /* may be NULL */, size_t cap,
+                   uint64_t *total_out,
+                   double *kernel_ms_out /* may be NULL */);
+
+/*
  * Host-side record splitter (no GPU work): what Bio.SeqIO.parse does for kmerdb/parse.py:50-85 on this path.
  * FASTQ: parses whole records of text[0, n) into bases_out (concatenated residues) and offsets_out
  * (nreads+1 entries); *consumed_out = bytes of text used (stops before a trailing partial record unless at_eof).

@@ -1,6 +1,6 @@
 // kdb_analysis_host.hip.h -- host side of the analysis calls of include/kdbhip.h, the ones that take finished vectors and no kdb_engine:
 // kdb_gram, kdb_pairstats, kdb_pairfloat, kdb_size_factors, kdb_scale_counts, kdb_spectrum, kdb_rank_transform, kdb_strand_merge,
-// kdb_score_reads and kdb_record_tables (which takes residues alone).  Every call works in an AnalysisCall: its own stream, events and
+// kdb_score_reads, and kdb_record_tables and kdb_minimizers (which take residues alone).  Every call works in an AnalysisCall: its own stream, events and
 // scratch, gone when it returns.  What the host alone decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -24,6 +24,7 @@
 #include "kdb_strands.hip.h"
 #include "kdb_score.hip.h"
 #include "kdb_tables.hip.h"
+#include "kdb_minimizers.hip.h"
 #include "kdb_sweep_plan.cpp.h"
 
 namespace {
@@ -193,6 +194,22 @@ int spectrum_sweep(AnalysisCall &call, const SpectrumScratch &sc, const void *d_
     for (uint32_t v = 0; v < kdbspectrum::DENSE; v++) total += host[v];
     if (total != nbins) return fail(KDB_ERR_HIP, "the spectrum holds %llu bins, the vector %llu", (unsigned long long)total, (unsigned long long)nbins);
     return KDB_OK;
+}
+
+// how many of the nbytes residues are not one of upper-case ACGTN
+// (a block at a time into one byte, which the compiler keeps in byte lanes: 4-5 x the rate of counting into 64 bits; a block is
+// counted only where it holds an offender)
+uint64_t residues_outside_acgtn(const uint8_t *bases, size_t nbytes)
+{
+    uint64_t nbad = 0;
+    auto outside = [](uint8_t b) { return !((b == 'A') | (b == 'C') | (b == 'G') | (b == 'T') | (b == 'N')); };
+    for (size_t at = 0; at < nbytes; at += 4096) {
+        const size_t n = std::min<size_t>(4096, nbytes - at);
+        uint8_t any = 0;
+        for (size_t i = 0; i < n; i++) any |= (uint8_t)outside(bases[at + i]);
+        if (any) for (size_t i = 0; i < n; i++) nbad += outside(bases[at + i]);
+    }
+    return nbad;
 }
 
 }  // namespace
@@ -643,17 +660,7 @@ int kdb_record_tables(int device_id, int k, int stride, int canonical, uint64_t 
                                  : bad == kdbplan::LAYOUT_ENDS  ? "read_offsets must start at 0 and end at nbytes"
                                                                 : "read_offsets must rise from 0 to nbytes");
     // so are the residues: every byte is one of ACGTN, or nothing is launched
-    // (a block at a time into one byte, which the compiler keeps in byte lanes: 4-5 x the rate of counting into 64 bits; a block is
-    // counted only where it holds an offender)
-    uint64_t nbad = 0;
-    auto outside = [](uint8_t b) { return !((b == 'A') | (b == 'C') | (b == 'G') | (b == 'T') | (b == 'N')); };
-    for (size_t at = 0; at < nbytes; at += 4096) {
-        const size_t n = std::min<size_t>(4096, nbytes - at);
-        uint8_t any = 0;
-        for (size_t i = 0; i < n; i++) any |= (uint8_t)outside(bases[at + i]);
-        if (any) for (size_t i = 0; i < n; i++) nbad += outside(bases[at + i]);
-    }
-    if (nbad) return fail(KDB_ERR_BAD_RESIDUE, "kdb_record_tables: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
+    if (const uint64_t nbad = residues_outside_acgtn(bases, nbytes)) return fail(KDB_ERR_BAD_RESIDUE, "kdb_record_tables: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
     const uint64_t npieces = lay.npieces, nbins = 1ull << (2 * k), nmulti = lay.multi.size();
     AnalysisCall call;
     if (int rc = call.open(device_id)) return rc;
@@ -693,6 +700,92 @@ int kdb_record_tables(int device_id, int k, int stride, int canonical, uint64_t 
     HIP_TRY(hipMemcpyAsync(last_id_out, ends + nreads, nreads * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
     HIP_TRY(hipStreamSynchronize(call.st));
     HIP_TRY(call.elapsed(kernel_ms_out));
+    return KDB_OK;
+}
+
+// ---- the (w,k)-minimizers of every record (kdb_minimizers.hip.h) ----
+int kdb_minimizers(int device_id, int k, int w, int canonical, int order, const uint8_t *bases, size_t nbytes, const uint64_t *offs, size_t nreads,
+                   uint64_t *counts_out, uint64_t *ids_out, uint32_t *pos_out, uint8_t *strand_out, size_t cap, uint64_t *total_out, double *kernel_ms_out)
+{
+    namespace km = kdbminimizers;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (k < 1 || k > km::MAX_K) return fail(KDB_ERR_ARG, "kdb_minimizers: k=%d out of range 1..%d", k, km::MAX_K);
+    if (w < 1 || w > km::MAX_W) return fail(KDB_ERR_ARG, "kdb_minimizers: w=%d out of range 1..%d", w, km::MAX_W);
+    if (order != KDB_MINIMIZER_LEX && order != KDB_MINIMIZER_HASHED) return fail(KDB_ERR_ARG, "kdb_minimizers: unknown order %d", order);
+    if (!total_out) return fail(KDB_ERR_ARG, "kdb_minimizers: total_out must not be NULL");
+    if (nreads == 0) {
+        if (nbytes != 0) return fail(KDB_ERR_ARG, "kdb_minimizers: residues but no records");
+        *total_out = 0;
+        return KDB_OK;
+    }
+    if (!offs || (!bases && nbytes) || !counts_out) return fail(KDB_ERR_ARG, "kdb_minimizers: NULL buffer");
+    if (cap > 0 && (!ids_out || !pos_out)) return fail(KDB_ERR_ARG, "kdb_minimizers: ids_out and pos_out must not be NULL where cap > 0");
+    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_minimizers: at most 2^30 residues per call");
+    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_minimizers: at most 2^30 records per call");
+    // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
+    kdbplan::MinimizersLayout lay;
+    if (const kdbplan::LayoutError bad = kdbplan::minimizers_layout(offs, nreads, nbytes, k, (uint32_t)w, km::PIECE, lay))
+        return fail(KDB_ERR_ARG, bad == kdbplan::LAYOUT_ENDS ? "read_offsets must start at 0 and end at nbytes" : "read_offsets must rise from 0 to nbytes");
+    // so are the residues: every byte is one of ACGTN, or nothing is launched
+    if (const uint64_t nbad = residues_outside_acgtn(bases, nbytes)) return fail(KDB_ERR_BAD_RESIDUE, "kdb_minimizers: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
+    const uint32_t npieces = (uint32_t)lay.npieces, nblocks = (npieces + km::SCAN_BLOCK - 1) / km::SCAN_BLOCK;
+    const bool multi = !lay.piece_rec.empty();
+    AnalysisCall call;
+    if (int rc = call.open(device_id)) return rc;
+
+    // (select_kernel's aligned words reach 3 bytes past a record's end, emit_kernel's five 39 bytes past a window's start)
+    auto *d_bases = call.alloc<uint8_t>(((nbytes + 15) & ~(size_t)15) + 64);
+    auto *d_offs = call.alloc<uint64_t>(nreads + 1);
+    auto *rec_piece0 = call.alloc<uint32_t>(nreads + 1), *piece_rec = multi ? call.alloc<uint32_t>(npieces) : nullptr;
+    auto *flags = call.alloc<uint8_t>(nbytes + 16);
+    auto *piece_count = call.alloc<uint32_t>(npieces), *piece_off = call.alloc<uint32_t>((uint64_t)npieces + 1), *sums = call.alloc<uint32_t>(nblocks);
+    auto *counts = call.alloc<unsigned long long>(nreads);
+    if (!d_bases || !d_offs || !rec_piece0 || (multi && !piece_rec) || !flags || !piece_count || !piece_off || !sums || !counts)
+        return fail(KDB_ERR_NOMEM, "kdb_minimizers: no room for the scratch of %zu residues in %zu records", nbytes, nreads);
+    if (nbytes) HIP_TRY(hipMemcpyAsync(d_bases, bases, nbytes, hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(rec_piece0, lay.rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    if (multi) HIP_TRY(hipMemcpyAsync(piece_rec, lay.piece_rec.data(), (size_t)npieces * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    const dim3 piece_grid((npieces + km::WAVES - 1) / km::WAVES);
+    uint32_t total = 0;
+    HIP_TRY(call.begin());
+    hipLaunchKernelGGL(km::select_kernel, piece_grid, dim3(km::TPB), (size_t)km::WAVES * lay.lds_wave, call.st, (const uint8_t *)d_bases, (const uint64_t *)d_offs,
+                       (const uint32_t *)piece_rec, (const uint32_t *)rec_piece0, npieces, k, (uint32_t)w, canonical ? 1 : 0, order, lay.max_keys, lay.lds_wave, flags,
+                       piece_count);
+    hipLaunchKernelGGL(km::scan_sums_kernel, dim3(nblocks), dim3(km::SCAN_TPB), 0, call.st, (const uint32_t *)piece_count, npieces, sums);
+    hipLaunchKernelGGL(km::scan_top_kernel, dim3(1), dim3(km::SCAN_TPB), 0, call.st, sums, nblocks, piece_off + npieces);
+    hipLaunchKernelGGL(km::scan_apply_kernel, dim3(nblocks), dim3(km::SCAN_TPB), 0, call.st, (const uint32_t *)piece_count, npieces, (const uint32_t *)sums, piece_off);
+    hipLaunchKernelGGL(km::record_counts_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, call.st, (const uint32_t *)piece_off,
+                       (const uint32_t *)rec_piece0, (uint64_t)nreads, counts);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(call.end());
+    HIP_TRY(hipMemcpyAsync(&total, piece_off + npieces, sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    HIP_TRY(call.elapsed(kernel_ms_out));
+    // the lists, where the caller's arrays hold them
+    uint64_t *d_ids = nullptr;
+    uint32_t *d_pos = nullptr;
+    uint8_t *d_strand = nullptr;
+    const bool emit = total > 0 && (uint64_t)total <= (uint64_t)cap;
+    if (emit) {
+        d_ids = call.alloc<uint64_t>(total);
+        d_pos = call.alloc<uint32_t>(total);
+        d_strand = strand_out ? call.alloc<uint8_t>(total) : nullptr;
+        if (!d_ids || !d_pos || (strand_out && !d_strand)) return fail(KDB_ERR_NOMEM, "kdb_minimizers: no room for the lists of %u minimizers", total);
+        HIP_TRY(call.begin());
+        hipLaunchKernelGGL(km::emit_kernel, piece_grid, dim3(km::TPB), 0, call.st, (const uint8_t *)d_bases, (const uint64_t *)d_offs, (const uint32_t *)piece_rec,
+                           (const uint32_t *)rec_piece0, npieces, k, canonical ? 1 : 0, (const uint8_t *)flags, (const uint32_t *)piece_off, (unsigned long long *)d_ids,
+                           d_pos, d_strand);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(call.end());
+        HIP_TRY(hipMemcpyAsync(ids_out, d_ids, (size_t)total * sizeof(uint64_t), hipMemcpyDeviceToHost, call.st));
+        HIP_TRY(hipMemcpyAsync(pos_out, d_pos, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        if (strand_out) HIP_TRY(hipMemcpyAsync(strand_out, d_strand, (size_t)total, hipMemcpyDeviceToHost, call.st));
+    }
+    HIP_TRY(hipMemcpyAsync(counts_out, counts, nreads * sizeof(uint64_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    if (emit) HIP_TRY(call.elapsed(kernel_ms_out));
+    *total_out = total;
     return KDB_OK;
 }
 

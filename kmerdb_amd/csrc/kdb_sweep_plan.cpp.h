@@ -1,7 +1,7 @@
 // kdb_sweep_plan.cpp.h -- the host-only plans of the analysis calls (plain C++, no HIP: tests/c/sweep_plan_check.cpp compiles it alone, runs
 // it under the sanitizers and prints the plans for tests/sweep_cases.py to be compared with): which block pairs become which launch rows,
 // in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, and how the records of
-// kdb_score_reads and of kdb_record_tables (tests/c/tables_plan_check.cpp) split into pieces.  The block size, HALF, the chunk sizes and the piece size are arguments: the kernel headers have them.
+// kdb_score_reads, of kdb_record_tables (tests/c/tables_plan_check.cpp) and of kdb_minimizers (tests/c/minimizers_plan_check.cpp) split into pieces.  The block size, HALF, the chunk sizes and the piece size are arguments: the kernel headers have them.
 // A row type is the kernel header's (kdbgram::Row, kdbpair::Row, kdbpair::FloatRow) or any struct of as many uint8_t fields.
 #pragma once
 #include <cstdint>
@@ -165,6 +165,64 @@ inline LayoutError tables_layout(const uint64_t *offs, size_t nreads, uint64_t n
     }
     lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
     if (!lay.multi.empty()) {
+        lay.piece_rec.resize(lay.npieces);
+        for (size_t r = 0; r < nreads; r++)
+            for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
+    }
+    return LAYOUT_OK;
+}
+
+// kdb_minimizers: a record of len residues has the start positions 0 .. len - k (constexpr: the kernels count them with the same expression)
+constexpr uint64_t minimizer_positions(uint64_t len, int k) { return len >= (uint64_t)k ? len - (uint64_t)k + 1 : 0; }
+
+// Piece p_in_rec of a record of nwin start positions OWNS the positions [first, first + count) -- it alone decides whether they are
+// selected -- and for that READS the keys of the positions [lo, hi): its own and up to w - 1 on either side, cut at the record's ends.
+// The residues behind those keys are [lo, hi + k - 1) of the record, all inside it.
+struct MinimizerPiece { uint64_t first, lo, hi; uint32_t count; };
+
+constexpr MinimizerPiece minimizer_piece(uint64_t nwin, uint32_t p_in_rec, uint32_t piece, uint32_t w)
+{
+    const uint64_t first = (uint64_t)p_in_rec * piece;
+    const uint64_t left = nwin > first ? nwin - first : 0;
+    const uint32_t count = (uint32_t)(left < (uint64_t)piece ? left : (uint64_t)piece);
+    const uint64_t halo = (uint64_t)w - 1;
+    const uint64_t lo = count == 0 ? first : (first > halo ? first - halo : 0);
+    const uint64_t hi = count == 0 ? first : (first + count + halo < nwin ? first + count + halo : nwin);
+    return MinimizerPiece{first, lo, hi, count};
+}
+
+// Record r is pieces rec_piece0[r] .. rec_piece0[r + 1], of at most `piece` start positions each and at least one (a record without a
+// start position has an empty one); piece_rec[p] = the record of piece p, left empty when every record is one piece.  max_keys: the most
+// keys any piece reads; lds_wave: the bytes of LDS a wave then needs, a multiple of 8 -- max_keys keys of 8 bytes, then the residues
+// behind them, read as aligned 4-byte words (up to 3 bytes before the first and after the last).
+struct MinimizersLayout {
+    std::vector<uint32_t> rec_piece0, piece_rec;
+    uint64_t npieces = 0;
+    uint32_t max_keys = 0, lds_wave = 0;
+};
+
+inline LayoutError minimizers_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, int k, uint32_t w, uint32_t piece, MinimizersLayout &lay)
+{
+    lay = MinimizersLayout();
+    if (offs[0] != 0 || offs[nreads] != nbytes) return LAYOUT_ENDS;
+    for (size_t r = 0; r < nreads; r++)
+        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
+    lay.rec_piece0.resize(nreads + 1);
+    bool multi = false;
+    for (size_t r = 0; r < nreads; r++) {
+        const uint64_t nwin = minimizer_positions(offs[r + 1] - offs[r], k);
+        const uint64_t n = std::max<uint64_t>(1, (nwin + piece - 1) / piece);
+        lay.rec_piece0[r] = (uint32_t)lay.npieces;
+        lay.npieces += n;                                                         // (< 2^31: 2^30 records and 2^30 positions at most)
+        multi = multi || n > 1;
+        for (uint64_t p = 0; p < n; p++) {
+            const MinimizerPiece pc = minimizer_piece(nwin, (uint32_t)p, piece, w);
+            lay.max_keys = std::max(lay.max_keys, (uint32_t)(pc.hi - pc.lo));
+        }
+    }
+    lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
+    lay.lds_wave = lay.max_keys * 8u + ((lay.max_keys + (uint32_t)k + 6u + 7u) & ~7u);
+    if (multi) {
         lay.piece_rec.resize(lay.npieces);
         for (size_t r = 0; r < nreads; r++)
             for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;

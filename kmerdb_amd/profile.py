@@ -240,6 +240,14 @@ def build_parser():
     cp.add_argument("--output-delimiter", default="\t")
     cp.add_argument("--device", type=int, default=0)
     cp.add_argument("seqfile", help=".fasta or .fastq (optionally gzipped)")
+    zp = sub.add_parser("minimizers", help="the (w,k)-minimizers of every record of a FASTA/FASTQ file: `seq_id<TAB>pos<TAB>kmer_id<TAB>+|-` lines")
+    zp.add_argument("-k", type=int, required=True, help="1..31")
+    zp.add_argument("-w", "--window-size", dest="w", type=int, required=True, help="consecutive start positions per run, 1..256")
+    zp.add_argument("--do-not-canonicalize", action="store_true", help="forward ids, not the smaller of both strands'")
+    zp.add_argument("--order", choices=["lexicographic", "hashed"], default="lexicographic", help="what is minimised: the id, or the id under an invertible mix")
+    zp.add_argument("-o", "--output", default=None, help="write to this file instead of stdout (the reference writes <name>.kdbi.1)")
+    zp.add_argument("--device", type=int, default=0)
+    zp.add_argument("seqfile", help=".fasta or .fastq (optionally gzipped)")
     kp = sub.add_parser("codons", help="codon counts of every CDS of a FASTA file (__init__.py:214-299)")
     kp.add_argument("--as-frequencies", action="store_true", help="frequencies inside the synonymous families instead of counts")
     kp.add_argument("--ignore-invalid-cds", action="store_true", help="leave out sequences whose length is not divisible by 3")
@@ -268,13 +276,23 @@ def build_parser():
 def main(argv=None):
     """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
     `graph`, `distance <metric> a.kdb b.kdb ...`, `matrix <method> a.kdb b.kdb ...`, `spectrum a.kdb ...` and
-    `probability <seqfile> <kdb>` beside it; `composition -k K seqfile`, `codons fasta` and `CUB --sequences fasta table` count per record."""
+    `probability <seqfile> <kdb>` beside it; `composition -k K seqfile`, `codons fasta` and `CUB --sequences fasta table` count per record,
+    `minimizers -k K -w W seqfile` lists every record's minimizers."""
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.cmd == "composition":
         from . import composition
         composition.composition(a.seqfile, a.k, canonical=not a.do_not_canonicalize, as_frequencies=a.as_frequencies,
                                 output_delimiter=a.output_delimiter, device=a.device)
+        return 0
+    if a.cmd == "minimizers":
+        from . import minimizer
+        kw = dict(canonical=not a.do_not_canonicalize, order=a.order, device=a.device)
+        if a.output is None:
+            minimizer.minimizers_table(a.seqfile, a.k, a.w, **kw)
+        else:
+            with open(a.output, "w") as f:
+                minimizer.minimizers_table(a.seqfile, a.k, a.w, out=f, **kw)
         return 0
     if a.cmd == "codons":
         from . import codons
