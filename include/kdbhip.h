@@ -473,6 +473,52 @@ int kdb_minimizers(int device_id, int k, int w, int canonical, int order,
                    double *kernel_ms_out /* may be NULL */);
 
 /*
+ * A batch of independent banded local alignments with affine gaps (csrc/kdb_align.hip.h): the extend step of
+ * seed-and-extend, for the seeds kdb_minimizers gives.  Per task the score and the four end coordinates; no traceback, no CIGAR.
+ * The reference's `alignment` subcommand (kmerdb/__init__.py:454-573) exits before it aligns; its score arguments are kept, nothing else.
+ * Query record x is q_bases[q_offsets[x] .. q_offsets[x + 1]), reference record y likewise in r_bases.  Task t aligns query task_q[t] to
+ * reference task_r[t]:
+ *   Q = the oriented query of length m: strand 0 the record q itself; strand 1 its reverse complement, Q[i] = comp(q[m - 1 - i]), N stays N
+ *   R = the reference record of length n;  d = task_diag[t]
+ *   cell (i, j), 0 <= i < m, 0 <= j < n, is IN BAND iff |(j - i) - d| <= band
+ *   s(i, j) = match if Q[i] = R[j] and both are one of A, C, G, T, else mismatch (an N matches nothing, not even an N)
+ *   anything not in band, or with a negative index, counts as -infinity for E and F and as 0 for H; over the in-band cells
+ *     E(i, j) = max(H(i, j - 1) + gap_open, E(i, j - 1) + gap_extend)
+ *     F(i, j) = max(H(i - 1, j) + gap_open, F(i - 1, j) + gap_extend)
+ *     H(i, j) = max(0, H(i - 1, j - 1) + s(i, j), E(i, j), F(i, j))          (gap_open is the cost of a gap's first residue)
+ *   ORIGINS: every finite H, E and F carries the cell where its alignment starts.  A cell whose H takes the diagonal term from a predecessor
+ *     with H = 0, or from no predecessor, starts at (i, j); the diagonal term otherwise inherits its predecessor's origin.  E and F inherit
+ *     the origin of the term that wins, the H + gap_open term on a tie.  H takes the origin of the first of [diagonal, E, F] that reaches
+ *     its value.  H = 0 has no origin.
+ *   BEST CELL: the largest H; on a tie the smallest i, then the smallest j.
+ *   score_out[t] = that H; qend_out[t] = i + 1, rend_out[t] = j + 1; (qstart_out[t], rstart_out[t]) = its origin.  Query coordinates are
+ *     those of the oriented query Q.  If no cell scores above 0 -- a band that misses the record, an empty record -- the score and all four
+ *     coordinates are 0, which is no error.
+ * All are exact integers and do not depend on the grid, on the other tasks or on the task's place among them.
+ * Limits: 1 <= band <= KDB_ALIGN_MAX_BAND; 1 <= match <= 127; -127 <= mismatch, gap_open, gap_extend <= 0; a query record holds at most
+ * KDB_ALIGN_MAX_QUERY = 2^20 residues (a score stays below 2^27); at most 2^30 residues per buffer and 2^26 tasks.
+ * All pointers: host memory.  Synchronous; scratch is allocated and freed inside the call.
+ * KDB_ERR_ARG, all settled on the host before anything is launched: a limit above, a NULL pointer (a residue buffer of 0 bytes may be
+ * NULL), offsets that do not start at 0, end at the buffer's size and rise, a task index that names no record, a strand above 1.
+ * KDB_ERR_BAD_RESIDUE: a byte outside upper-case ACGTN in either buffer; no output is written (as kdb_minimizers).
+ * KDB_ERR_NOMEM: the scratch does not fit.  ntasks = 0: KDB_OK once the scalars are in range.  kernel_ms_out (may be NULL): device time
+ * of the kernel, by HIP events.
+ * KDB_ALIGN_STAGE: the anti-diagonal steps a wave takes between two refills of its residues in LDS; KDB_ALIGN_GRID_MAX: the most
+ * workgroups of a launch, 4 tasks under way in each.
+ */
+#define KDB_ALIGN_MAX_BAND   63
+#define KDB_ALIGN_MAX_QUERY  1048576
+#define KDB_ALIGN_STAGE      512
+#define KDB_ALIGN_GRID_MAX   4096
+int kdb_align_banded(int device_id,
+                     const uint8_t *q_bases, size_t q_nbytes, const uint64_t *q_offsets, size_t nq,
+                     const uint8_t *r_bases, size_t r_nbytes, const uint64_t *r_offsets, size_t nr,
+                     const uint32_t *task_q, const uint32_t *task_r, const int64_t *task_diag, const uint8_t *task_strand, size_t ntasks,
+                     int band, int match, int mismatch, int gap_open, int gap_extend,
+                     int32_t *score_out, uint32_t *qstart_out, uint32_t *qend_out, uint32_t *rstart_out, uint32_t *rend_out /* ntasks each */,
+                     double *kernel_ms_out /* may be NULL */);
+
+/*
  * Host-side record splitter (no GPU work): what Bio.SeqIO.parse does for kmerdb/parse.py:50-85 on this path.
  * FASTQ: parses whole records of text[0, n) into bases_out (concatenated residues) and offsets_out
  * (nreads+1 entries); *consumed_out = bytes of text used (stops before a trailing partial record unless at_eof).

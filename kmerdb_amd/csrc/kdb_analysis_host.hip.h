@@ -1,6 +1,6 @@
 // kdb_analysis_host.hip.h -- host side of the analysis calls of include/kdbhip.h, the ones that take finished vectors and no kdb_engine:
 // kdb_gram, kdb_pairstats, kdb_pairfloat, kdb_size_factors, kdb_scale_counts, kdb_spectrum, kdb_rank_transform, kdb_strand_merge,
-// kdb_score_reads, and kdb_record_tables and kdb_minimizers (which take residues alone).  Every call works in an AnalysisCall: its own stream, events and
+// kdb_score_reads, and kdb_record_tables, kdb_minimizers and kdb_align_banded (which take residues alone).  Every call works in an AnalysisCall: its own stream, events and
 // scratch, gone when it returns.  What the host alone decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,6 +25,7 @@
 #include "kdb_score.hip.h"
 #include "kdb_tables.hip.h"
 #include "kdb_minimizers.hip.h"
+#include "kdb_align.hip.h"
 #include "kdb_sweep_plan.cpp.h"
 
 namespace {
@@ -786,6 +787,76 @@ int kdb_minimizers(int device_id, int k, int w, int canonical, int order, const 
     HIP_TRY(hipStreamSynchronize(call.st));
     if (emit) HIP_TRY(call.elapsed(kernel_ms_out));
     *total_out = total;
+    return KDB_OK;
+}
+
+// ---- banded local alignments, a wave per task (kdb_align.hip.h) ----
+int kdb_align_banded(int device_id, const uint8_t *q_bases, size_t q_nbytes, const uint64_t *q_offs, size_t nq, const uint8_t *r_bases, size_t r_nbytes,
+                     const uint64_t *r_offs, size_t nr, const uint32_t *task_q, const uint32_t *task_r, const int64_t *task_diag, const uint8_t *task_strand,
+                     size_t ntasks, int band, int match, int mismatch, int gap_open, int gap_extend, int32_t *score_out, uint32_t *qstart_out, uint32_t *qend_out,
+                     uint32_t *rstart_out, uint32_t *rend_out, double *kernel_ms_out)
+{
+    namespace ka = kdbalign;
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (band < 1 || band > ka::MAX_BAND) return fail(KDB_ERR_ARG, "kdb_align_banded: band=%d out of range 1..%d", band, ka::MAX_BAND);
+    if (match < 1 || match > 127) return fail(KDB_ERR_ARG, "kdb_align_banded: match=%d out of range 1..127", match);
+    if (mismatch < -127 || mismatch > 0 || gap_open < -127 || gap_open > 0 || gap_extend < -127 || gap_extend > 0)
+        return fail(KDB_ERR_ARG, "kdb_align_banded: mismatch=%d, gap_open=%d, gap_extend=%d: each must lie in -127..0", mismatch, gap_open, gap_extend);
+    if (ntasks == 0) return KDB_OK;
+    if (!q_offs || !r_offs || (!q_bases && q_nbytes) || (!r_bases && r_nbytes) || !task_q || !task_r || !task_diag || !task_strand || !score_out || !qstart_out ||
+        !qend_out || !rstart_out || !rend_out)
+        return fail(KDB_ERR_ARG, "kdb_align_banded: NULL buffer");
+    if (q_nbytes > (1ull << 30) || r_nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_align_banded: at most 2^30 residues per buffer");
+    if (nq > (1ull << 30) || nr > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_align_banded: at most 2^30 records per buffer");
+    if (ntasks > (1ull << 26)) return fail(KDB_ERR_ARG, "kdb_align_banded: at most 2^26 tasks per call");
+    // every address the kernel forms is settled here: the offsets and the tasks are host memory
+    kdbplan::AlignLayout lay;
+    if (const kdbplan::LayoutError bad = kdbplan::align_layout(q_offs, nq, q_nbytes, r_offs, nr, r_nbytes, task_q, task_r, task_diag, task_strand, ntasks, (uint32_t)band,
+                                                               ka::MAX_QUERY, ka::WAVES, ka::GRID_MAX, lay)) {
+        if (bad == kdbplan::LAYOUT_ENDS) return fail(KDB_ERR_ARG, "kdb_align_banded: offsets must start at 0 and end at the buffer's size");
+        if (bad == kdbplan::LAYOUT_RISE) return fail(KDB_ERR_ARG, "kdb_align_banded: offsets must rise from 0 to the buffer's size");
+        if (bad == kdbplan::LAYOUT_TASK) return fail(KDB_ERR_ARG, "kdb_align_banded: task %llu names a record that is not there", (unsigned long long)lay.bad);
+        if (bad == kdbplan::LAYOUT_STRAND) return fail(KDB_ERR_ARG, "kdb_align_banded: task %llu has a strand that is neither 0 nor 1", (unsigned long long)lay.bad);
+        return fail(KDB_ERR_ARG, "kdb_align_banded: the query of task %llu holds more than 2^20 residues", (unsigned long long)lay.bad);
+    }
+    // so are the residues: every byte is one of ACGTN, or nothing is launched
+    if (const uint64_t nbad = residues_outside_acgtn(q_bases, q_nbytes) + residues_outside_acgtn(r_bases, r_nbytes))
+        return fail(KDB_ERR_BAD_RESIDUE, "kdb_align_banded: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
+    AnalysisCall call;
+    if (int rc = call.open(device_id)) return rc;
+
+    const uint64_t q_nwords = (q_nbytes + 3) / 4, r_nwords = (r_nbytes + 3) / 4;                 // (the kernel reads whole words, and none outside these)
+    auto *d_q = call.alloc<uint32_t>(q_nwords + 4), *d_r = call.alloc<uint32_t>(r_nwords + 4);
+    auto *d_qoffs = call.alloc<uint64_t>(nq + 1), *d_roffs = call.alloc<uint64_t>(nr + 1);
+    auto *d_tq = call.alloc<uint32_t>(ntasks), *d_tr = call.alloc<uint32_t>(ntasks);
+    auto *d_diag = call.alloc<int64_t>(ntasks);
+    auto *d_strand = call.alloc<uint8_t>(ntasks);
+    auto *d_out = call.alloc<uint32_t>(5 * (uint64_t)ntasks);
+    if (!d_q || !d_r || !d_qoffs || !d_roffs || !d_tq || !d_tr || !d_diag || !d_strand || !d_out)
+        return fail(KDB_ERR_NOMEM, "kdb_align_banded: no room for %zu + %zu residues and %zu tasks", q_nbytes, r_nbytes, ntasks);
+    if (q_nbytes) HIP_TRY(hipMemcpyAsync(d_q, q_bases, q_nbytes, hipMemcpyHostToDevice, call.st));
+    if (r_nbytes) HIP_TRY(hipMemcpyAsync(d_r, r_bases, r_nbytes, hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_qoffs, q_offs, (nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_roffs, r_offs, (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_tq, task_q, ntasks * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_tr, task_r, ntasks * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_diag, task_diag, ntasks * sizeof(int64_t), hipMemcpyHostToDevice, call.st));
+    HIP_TRY(hipMemcpyAsync(d_strand, task_strand, ntasks, hipMemcpyHostToDevice, call.st));
+    uint32_t *o_score = d_out, *o_qs = d_out + ntasks, *o_qe = d_out + 2 * ntasks, *o_rs = d_out + 3 * ntasks, *o_re = d_out + 4 * ntasks;
+    HIP_TRY(call.begin());
+    hipLaunchKernelGGL(ka::align_kernel, dim3(lay.grid), dim3(ka::TPB), (size_t)ka::WAVES * kdbplan::align_lds_wave(ka::STAGE), call.st, (const uint32_t *)d_q,
+                       (int64_t)q_nwords, (const uint64_t *)d_qoffs, (const uint32_t *)d_r, (int64_t)r_nwords, (const uint64_t *)d_roffs, (const uint32_t *)d_tq,
+                       (const uint32_t *)d_tr, (const int64_t *)d_diag, (const uint8_t *)d_strand, (uint32_t)ntasks, band, match, mismatch, gap_open, gap_extend,
+                       (int32_t *)o_score, o_qs, o_qe, o_rs, o_re);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(call.end());
+    HIP_TRY(hipMemcpyAsync(score_out, o_score, ntasks * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(qstart_out, o_qs, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(qend_out, o_qe, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(rstart_out, o_rs, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipMemcpyAsync(rend_out, o_re, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    HIP_TRY(call.elapsed(kernel_ms_out));
     return KDB_OK;
 }
 

@@ -30,6 +30,7 @@
 #include "kdb_score.hip.h"
 #include "kdb_tables.hip.h"
 #include "kdb_minimizers.hip.h"
+#include "kdb_align.hip.h"
 #include "kdb_hostparse.cpp.h"
 #include "kdb_kdbwriter.cpp.h"
 

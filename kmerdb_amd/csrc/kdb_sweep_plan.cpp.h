@@ -1,7 +1,8 @@
 // kdb_sweep_plan.cpp.h -- the host-only plans of the analysis calls (plain C++, no HIP: tests/c/sweep_plan_check.cpp compiles it alone, runs
 // it under the sanitizers and prints the plans for tests/sweep_cases.py to be compared with): which block pairs become which launch rows,
 // in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, and how the records of
-// kdb_score_reads, of kdb_record_tables (tests/c/tables_plan_check.cpp) and of kdb_minimizers (tests/c/minimizers_plan_check.cpp) split into pieces.  The block size, HALF, the chunk sizes and the piece size are arguments: the kernel headers have them.
+// kdb_score_reads, of kdb_record_tables (tests/c/tables_plan_check.cpp) and of kdb_minimizers (tests/c/minimizers_plan_check.cpp) split into pieces,
+// and the window, the stages and the LDS of a task of kdb_align_banded (tests/c/alignment_plan_check.cpp).  The block size, HALF, the chunk sizes, the piece size and the stage are arguments: the kernel headers have them.
 // A row type is the kernel header's (kdbgram::Row, kdbpair::Row, kdbpair::FloatRow) or any struct of as many uint8_t fields.
 #pragma once
 #include <cstdint>
@@ -95,7 +96,8 @@ inline uint32_t rows_cap(uint32_t nrows, uint32_t many_rows, uint32_t cap, uint3
 // offsets into nbytes residues, nreads >= 1.  A record shorter than k counts as short unless it is the first and `continues` an earlier
 // call's; where there are short records piece_rec is left empty too: the caller refuses them.
 enum LayoutError { LAYOUT_OK = 0, LAYOUT_ENDS /* must start at 0 and end at nbytes */, LAYOUT_RISE /* must rise from 0 to nbytes */,
-                   LAYOUT_ENTRIES /* kdb_record_tables: more table entries than the call allows */ };
+                   LAYOUT_ENTRIES /* kdb_record_tables: more table entries than the call allows */,
+                   LAYOUT_TASK, LAYOUT_STRAND, LAYOUT_QUERY /* kdb_align_banded: a task's record index, its strand, its query's length */ };
 
 struct ScoreLayout {
     std::vector<uint32_t> rec_piece0, piece_rec;
@@ -227,6 +229,83 @@ inline LayoutError minimizers_layout(const uint64_t *offs, size_t nreads, uint64
         for (size_t r = 0; r < nreads; r++)
             for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
     }
+    return LAYOUT_OK;
+}
+
+// kdb_align_banded: a task aligns an oriented query of m residues to a reference record of n around the diagonal d, j - i = d, inside
+// |(j - i) - d| <= band.  With jb = d - band cell (i, j) lies on the band's diagonal c = j - i - jb, 0 <= c <= 2 band.
+//   [r_lo, r_hi): the reference residues the band can reach, [d - band, d + m - 1 + band] cut to [0, n)
+//   [i_lo, i_hi): the query rows that hold a cell both in the band and in the record; every other row is all zero
+// A task whose band misses the record, or with m = 0 or n = 0, is EMPTY: all six are 0.  Otherwise jb fits 32 bits: -m - 2 band < jb < n.
+// (constexpr: the kernel asks for the same window.)
+struct AlignWindow {
+    uint32_t r_lo, r_hi, i_lo, i_hi;
+    int32_t jb;
+    constexpr bool empty() const { return i_lo >= i_hi; }
+};
+
+constexpr AlignWindow align_window(uint64_t m, uint64_t n, int64_t d, uint32_t band)
+{
+    const int64_t far = (int64_t)1 << 32;                                         // (m <= 2^20, n <= 2^30: a diagonal out there meets nothing)
+    if (m == 0 || n == 0 || d >= far || d <= -far) return AlignWindow{0, 0, 0, 0, 0};
+    const int64_t jb = d - (int64_t)band, b2 = 2 * (int64_t)band;
+    const int64_t i_lo = -jb - b2 > 0 ? -jb - b2 : 0;
+    const int64_t i_hi = (int64_t)n - jb < (int64_t)m ? (int64_t)n - jb : (int64_t)m;
+    if (i_lo >= i_hi) return AlignWindow{0, 0, 0, 0, 0};
+    const int64_t r_lo = jb > 0 ? jb : 0;
+    const int64_t r_hi = jb + (int64_t)m + b2 < (int64_t)n ? jb + (int64_t)m + b2 : (int64_t)n;
+    return AlignWindow{(uint32_t)r_lo, (uint32_t)r_hi, (uint32_t)i_lo, (uint32_t)i_hi, (int32_t)jb};
+}
+
+// The wave sweeps anti-diagonals: in step T lane l works on row T - l, so the rows [i_lo, i_hi) take the steps [t_lo, t_hi), t_lo a
+// multiple of ALIGN_GROUP (the rows a lane takes from one pair of LDS reads), in stages of `stage` steps.  A stage that begins at step ts
+// holds in LDS the oriented query rows [ts - ALIGN_LANES, ts + stage) and the reference residues [ts - ALIGN_LANES + jb, + stage +
+// ALIGN_R_EXTRA) -- the lanes' rows and, ALIGN_LANES - 1 rows back and 2 ALIGN_LANES - 1 diagonals on, what the last group reads -- whatever
+// the band is; a row or residue outside the record is staged as a code that matches nothing.
+constexpr uint32_t ALIGN_LANES = 64, ALIGN_GROUP = 4, ALIGN_R_EXTRA = 2 * ALIGN_LANES + 8;
+constexpr uint32_t align_t_lo(const AlignWindow &w) { return w.i_lo & ~(ALIGN_GROUP - 1); }
+constexpr uint32_t align_t_hi(const AlignWindow &w, uint32_t band) { return w.i_hi + band; }
+constexpr uint32_t align_stages(const AlignWindow &w, uint32_t band, uint32_t stage)
+{
+    return w.empty() ? 0 : (align_t_hi(w, band) - align_t_lo(w) + stage - 1) / stage;
+}
+constexpr uint32_t align_lds_q(uint32_t stage) { return stage + ALIGN_LANES + 8; }    // (+ 8: a lane reads the two aligned words around its 4 rows)
+constexpr uint32_t align_lds_r(uint32_t stage) { return stage + ALIGN_R_EXTRA; }
+constexpr uint32_t align_lds_wave(uint32_t stage) { return align_lds_q(stage) + align_lds_r(stage); }     // a multiple of 8 where stage is
+
+// The batch: every offset array must start at 0, end at its buffer's size and rise; every task must name a query and a reference record
+// (LAYOUT_TASK, bad = the task) and a strand 0 or 1 (LAYOUT_STRAND), and its query holds at most max_query residues (LAYOUT_QUERY).
+// grid: workgroups of `waves` waves, a wave per task, at most grid_max of them (the waves then stride through the tasks).  cells: the sum
+// of m (2 band + 1) over the tasks, the figure the benchmark divides by.
+struct AlignLayout {
+    uint32_t grid = 0;
+    uint64_t cells = 0, nonempty = 0, bad = 0;
+};
+
+inline LayoutError align_layout(const uint64_t *q_offs, size_t nq, uint64_t q_nbytes, const uint64_t *r_offs, size_t nr, uint64_t r_nbytes, const uint32_t *task_q,
+                                const uint32_t *task_r, const int64_t *task_diag, const uint8_t *task_strand, size_t ntasks, uint32_t band, uint64_t max_query,
+                                uint32_t waves, uint32_t grid_max, AlignLayout &lay)
+{
+    lay = AlignLayout();
+    if (q_offs[0] != 0 || q_offs[nq] != q_nbytes || r_offs[0] != 0 || r_offs[nr] != r_nbytes) return LAYOUT_ENDS;
+    for (size_t r = 0; r < nq; r++)
+        if (q_offs[r + 1] < q_offs[r] || q_offs[r + 1] > q_nbytes) return LAYOUT_RISE;
+    for (size_t r = 0; r < nr; r++)
+        if (r_offs[r + 1] < r_offs[r] || r_offs[r + 1] > r_nbytes) return LAYOUT_RISE;
+    uint64_t cells = 0, nonempty = 0;
+    for (size_t t = 0; t < ntasks; t++) {
+        lay.bad = t;
+        if (task_q[t] >= nq || task_r[t] >= nr) return LAYOUT_TASK;
+        if (task_strand[t] > 1) return LAYOUT_STRAND;
+        const uint64_t m = q_offs[task_q[t] + 1] - q_offs[task_q[t]], n = r_offs[task_r[t] + 1] - r_offs[task_r[t]];
+        if (m > max_query) return LAYOUT_QUERY;
+        cells += m * (2 * (uint64_t)band + 1);
+        nonempty += align_window(m, n, task_diag[t], band).empty() ? 0 : 1;
+    }
+    lay.bad = 0;
+    lay.cells = cells;
+    lay.nonempty = nonempty;
+    lay.grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((ntasks + waves - 1) / waves, grid_max));
     return LAYOUT_OK;
 }
 

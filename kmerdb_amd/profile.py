@@ -248,6 +248,25 @@ def build_parser():
     zp.add_argument("-o", "--output", default=None, help="write to this file instead of stdout (the reference writes <name>.kdbi.1)")
     zp.add_argument("--device", type=int, default=0)
     zp.add_argument("seqfile", help=".fasta or .fastq (optionally gzipped)")
+    lp = sub.add_parser("alignment", help="seed-and-extend alignment of every query record to a reference FASTA: minimizer seeds, banded Smith-Waterman; "
+                                          "`qname qlen qstart qend +|- rname rlen rstart rend score seeds diag` lines, tab-separated")
+    lp.add_argument("-k", type=int, required=True, help="1..31")
+    lp.add_argument("-w", "--window-size", dest="w", type=int, required=True, help="consecutive start positions per minimizer run, 1..256")
+    lp.add_argument("--order", choices=["lexicographic", "hashed"], default="hashed", help="the minimizers' order")
+    lp.add_argument("--band", type=int, default=16, help="diagonals on either side of a candidate's, 1..63")
+    lp.add_argument("--match-score", type=int, default=3)
+    lp.add_argument("--mismatch-score", type=int, default=-1)
+    lp.add_argument("--gap-open", type=int, default=-10, help="the cost of a gap's first residue")
+    lp.add_argument("--gap-extend", type=int, default=-1, help="the cost of each further residue of a gap")
+    lp.add_argument("-n", "--num-mins", dest="min_seeds", type=int, default=2, help="minimizer hits a candidate needs")
+    lp.add_argument("--max-occ", type=int, default=50, help="reference minimizers that occur more often are left out of the sketch")
+    lp.add_argument("--max-candidates", type=int, default=4, help="candidates aligned per query")
+    lp.add_argument("--min-score", type=int, default=0)
+    lp.add_argument("--best-only", action="store_true", help="the best result of every query alone")
+    lp.add_argument("-o", "--output", default=None, help="write to this file instead of stdout")
+    lp.add_argument("--device", type=int, default=0)
+    lp.add_argument("reference", help="the reference, .fasta (optionally gzipped)")
+    lp.add_argument("query", help="the reads, .fasta or .fastq (optionally gzipped)")
     kp = sub.add_parser("codons", help="codon counts of every CDS of a FASTA file (__init__.py:214-299)")
     kp.add_argument("--as-frequencies", action="store_true", help="frequencies inside the synonymous families instead of counts")
     kp.add_argument("--ignore-invalid-cds", action="store_true", help="leave out sequences whose length is not divisible by 3")
@@ -277,7 +296,7 @@ def main(argv=None):
     """`python -m kmerdb_amd profile -k K -o NAME input` -- the reference's profile flags (__init__.py:2084-2107);
     `graph`, `distance <metric> a.kdb b.kdb ...`, `matrix <method> a.kdb b.kdb ...`, `spectrum a.kdb ...` and
     `probability <seqfile> <kdb>` beside it; `composition -k K seqfile`, `codons fasta` and `CUB --sequences fasta table` count per record,
-    `minimizers -k K -w W seqfile` lists every record's minimizers."""
+    `minimizers -k K -w W seqfile` lists every record's minimizers, `alignment -k K -w W reference query` aligns reads to a reference."""
     ap = build_parser()
     a = ap.parse_args(argv)
     if a.cmd == "composition":
@@ -293,6 +312,16 @@ def main(argv=None):
         else:
             with open(a.output, "w") as f:
                 minimizer.minimizers_table(a.seqfile, a.k, a.w, out=f, **kw)
+        return 0
+    if a.cmd == "alignment":
+        from . import alignment
+        kw = dict(k=a.k, w=a.w, order=a.order, band=a.band, match=a.match_score, mismatch=a.mismatch_score, gap_open=a.gap_open, gap_extend=a.gap_extend,
+                  min_seeds=a.min_seeds, max_occ=a.max_occ, max_candidates=a.max_candidates, min_score=a.min_score, best_only=a.best_only, device=a.device)
+        if a.output is None:
+            alignment.align_table(a.reference, a.query, **kw)
+        else:
+            with open(a.output, "w") as f:
+                alignment.align_table(a.reference, a.query, out=f, **kw)
         return 0
     if a.cmd == "codons":
         from . import codons
