@@ -55,6 +55,35 @@ def batch_tables(records, k, stride=1, canonical=False, phase=0, continues=False
             np.array([o[2] for o in out], dtype=np.uint64), np.array([o[3] for o in out], dtype=np.int32), np.array([o[4] for o in out], dtype=np.int32))
 
 
+def uniform_tables(block, k, stride=1, canonical=False):
+    """batch_tables (phase 0) for records of one length, the rows of the uint8 array `block` (records x length): every window of every
+    record in one array, the counts from one bincount over (record, id)"""
+    block = np.asarray(block, dtype=np.uint8)
+    n, length = block.shape
+    codes = CODE.astype(np.int8)[block]                                       # (small types: the block may hold tens of megabytes)
+    if np.any(codes == -2):
+        raise ValueError("a residue outside ACGTN")
+    p = window_starts(length, k, stride)
+    none = np.full(n, -1, dtype=np.int32)
+    if p.size == 0 or n == 0:
+        return np.zeros((n, 4 ** k), dtype=np.uint32), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), none, none.copy()
+    ok = np.ones((n, p.size), dtype=bool)
+    ids = np.zeros((n, p.size), dtype=np.int32)
+    for j in range(k):
+        c = codes[:, p + j]
+        ok &= c >= 0
+        ids = ids * 4 + np.maximum(c, 0)
+    if canonical:
+        ids = np.minimum(ids, rc_ids(ids, k).astype(np.int32))
+    rows, cols = np.nonzero(ok)
+    tables = np.bincount(rows * 4 ** k + ids[rows, cols], minlength=n * 4 ** k).astype(np.uint32).reshape(n, 4 ** k)
+    windows = ok.sum(axis=1)
+    at = np.arange(n)
+    first = np.where(windows > 0, ids[at, np.argmax(ok, axis=1)], -1)
+    last = np.where(windows > 0, ids[at, p.size - 1 - np.argmax(ok[:, ::-1], axis=1)], -1)
+    return tables, windows.astype(np.uint64), (p.size - windows).astype(np.uint64), first.astype(np.int32), last.astype(np.int32)
+
+
 def record_tables_stub(bases, offsets, k, stride=1, canonical=False, phase=0, continues=False, device=0):
     """the restatement behind the signature of kmerdb_amd.composition.record_tables: the CPU tests put it in the device call's place"""
     raw = bytes(bases)

@@ -258,6 +258,154 @@ def test_a_tasks_result_does_not_depend_on_the_batch(dev):
         assert tuple(int(g[0]) for g in dev.run([mine_q], [mine_r], [(0, 0, d, strand)], band)) == want
 
 
+# ---- the rows, scores and diagonals the packed origins and keys are sized for ----
+
+MAX_QUERY = _header_constant("KDB_ALIGN_MAX_QUERY")
+LETTERS = np.frombuffer(b"ACGT", dtype=np.uint8)
+
+
+def _substitute(rng, rec, p):
+    """a copy of rec with about p of its residues replaced by another letter (numpy: ac.mutate walks a megabase residue by residue)"""
+    s = np.frombuffer(bytes(rec), dtype=np.uint8).copy()
+    at = np.flatnonzero(rng.random(s.size) < p)
+    s[at] = LETTERS[(np.searchsorted(LETTERS, s[at]) + rng.integers(1, 4, size=at.size)) % 4]
+    return s.tobytes()
+
+
+def _both_strands(dev, x, ref, d, band, where, before=(b"ACGTTGCAN", b"GATTACA"), **scores):
+    """The task (x, ref, d) on strand 0, and on strand 1 with the query handed over as x's reverse complement: the oriented query is x both
+    times (ac.banded turns the record round first and is the same computation from there on), so one run of ac.banded is the reference
+    of both.  `before`: records ahead of the two in their buffers -> the reference's tuple"""
+    assert ac.orient(ac.orient(x, 1), 1) == x
+    want = ac.banded(x, ref, d, band, 0, **scores)
+    got = dev.run([before[0], x, ac.orient(x, 1)], [before[1], ref], [(1, 1, d, 0), (2, 1, d, 1)], band, **scores)
+    for strand in (0, 1):
+        assert tuple(int(g[strand]) for g in got) == want, (where, strand)
+    return want
+
+
+def test_a_query_of_the_largest_length(dev):
+    """m = KDB_ALIGN_MAX_QUERY: rows up to 2^20 - 1 in the origins and in the best cell's key, 2049 stages"""
+    rng = np.random.Generator(np.random.PCG64(1 << 20))
+    x = mc.random_record(rng, MAX_QUERY)
+    ref = _substitute(rng, x, 0.02)                                           # substitutions alone: the path stays on the diagonal
+    before = (mc.random_record(rng, 1001), mc.random_record(rng, 777))        # (the records begin at odd offsets, far into their buffers)
+    score, qstart, qend, rstart, rend = _both_strands(dev, x, ref, 0, 1, "2^20 rows", before)
+    assert score > 2 * MAX_QUERY and qend - qstart > MAX_QUERY - 1000 and (qend - qstart) == (rend - rstart)
+
+
+def test_the_largest_score_there_is(dev):
+    """127 x 2^20, above 2^26: the score's 27 bits beside the 27 of the best cell's place"""
+    rng = np.random.Generator(np.random.PCG64(127 << 20))
+    x = mc.random_record(rng, MAX_QUERY)
+    before = (mc.random_record(rng, 1001), mc.random_record(rng, 777))
+    scores = dict(match=127, mismatch=-127, gap_open=-127, gap_extend=-127)
+    out = dev.raw(mc.pack([before[0], x]), mc.pack([before[1], x]), ac.task_arrays([(1, 1, 0, 0)]), 2, ms=True, **scores)
+    want = ac.banded(x, x, 0, 2, 0, **scores)
+    assert out[0] == dev.OK and tuple(int(o[0]) for o in out[1:]) == want == (127 * MAX_QUERY, 0, MAX_QUERY, 0, MAX_QUERY) and want[0] > 2 ** 26
+
+
+FAR = (1 << 16) + 700
+
+
+def _far_row_cases(rng, top):
+    """three tasks of top + 700 rows whose origin or best cell lies beyond row `top` -> [(name, query, reference, d)]"""
+    x = mc.random_record(rng, top + 700)
+    tail, p = mc.random_record(rng, 650), top + 300
+    return [("an indel of three after row top", x, _substitute(rng, x[:top + 100] + b"ACG" + x[top + 100:], 0.01), 0),
+            ("the origin beyond row top", b"A" * (top + 50) + tail, b"C" * (top + 55) + tail, 5),
+            ("the best cell beyond row top", x[:p] + mc.random_record(rng, 400), x[:p] + mc.random_record(rng, 400), 0)]
+
+
+@pytest.mark.parametrize("case", [0, 1, 2])
+def test_origins_and_best_cells_beyond_row_65536(dev, case):
+    """rows that do not fit 16 bits in an origin (cases 0 and 1) and in the best cell (all three), on both strands"""
+    name, x, ref, d = _far_row_cases(np.random.Generator(np.random.PCG64(65536)), 1 << 16)[case]
+    assert len(x) == FAR
+    score, qstart, qend, rstart, rend = _both_strands(dev, x, ref, d, 8, name, match=3, mismatch=-4, gap_open=-10, gap_extend=-1)
+    if case == 0:
+        assert (qstart, rstart, qend, rend) == (0, 0, FAR, FAR + 3) and score > 2 * FAR
+    elif case == 1:
+        assert (qstart, rstart, qend, rend, score) == ((1 << 16) + 50, (1 << 16) + 55, FAR, FAR + 5, 3 * 650)
+    else:
+        assert qstart == 0 and (1 << 16) + 300 <= qend < (1 << 16) + 320 and rend == qend and score >= 3 * ((1 << 16) + 300)
+
+
+def test_an_origin_beyond_row_524288(dev):
+    """bit 19 of the row is set in the origin and in the best cell"""
+    top = 1 << 19
+    name, x, ref, d = _far_row_cases(np.random.Generator(np.random.PCG64(524288)), top)[1]
+    assert _both_strands(dev, x, ref, d, 1, name) == (3 * 650, top + 50, top + 700, top + 55, top + 705)
+
+
+def test_the_tie_rule_between_row_0_and_row_524288(dev):
+    """Two segments of one score, one at row 0 and one beyond row 2^19, nothing worth having between them: the smaller row wins, on one
+    diagonal (one lane's own `>`) and on two (the wave's reduction of (score, -row, -diagonal)); the far one wins where it is one match
+    longer."""
+    n = 1 << 19
+    seg = b"GCTGACTCGTGACCTGATCGTGCTAGTCGATGCGTCAGTC"
+    assert len(seg) == 40 and 3 * len(seg) % 8 == 0
+    q = seg + b"A" * n + seg
+    one = ac.banded(q, seg + b"C" * n + seg, 0, 1)
+    two = ac.banded(q, seg + b"C" * (n + 1) + seg, 0, 1)
+    far = ac.banded(q + b"G", seg + b"C" * (n + 1) + seg + b"G", 0, 1)
+    assert one == two == (120, 0, 40, 0, 40) and far == (123, 40 + n, 81 + n, 41 + n, 82 + n)
+    got = dev.run([q, q + b"G"], [seg + b"C" * n + seg, seg + b"C" * (n + 1) + seg, seg + b"C" * (n + 1) + seg + b"G"], [(0, 0, 0, 0), (0, 1, 0, 0), (1, 2, 0, 0)], 1)
+    assert [tuple(int(g[t]) for g in got) for t in range(3)] == [one, two, far]
+
+
+def test_every_diagonal_of_the_widest_band_over_forty_stages(dev):
+    """all 127 diagonals, 64 lanes, and a path that keeps changing lanes while the wave refills its residues forty times"""
+    rng = np.random.Generator(np.random.PCG64(20000))
+    x = mc.random_record(rng, 20000, 0.001)
+    ref = ac.mutate(rng, x, 0.02, 0.01)                                       # indels: the path wanders from lane to lane
+    assert 20000 + MAX_BAND > 39 * S and abs(len(ref) - len(x)) < MAX_BAND
+    score, qstart, qend, rstart, rend = _both_strands(dev, x, ref, 0, MAX_BAND, "widest band", match=3, mismatch=-1, gap_open=-4, gap_extend=-1)
+    assert qend - qstart > 19000 and score > 40000
+
+
+def test_far_diagonals_in_a_record_of_sixteen_million_residues(dev):
+    """jb = d - band up to 2^24 and beyond, in a record that is not the buffer's first"""
+    rng = np.random.Generator(np.random.PCG64(1 << 24))
+    n, band = (1 << 24) + 1000, 16
+    big = LETTERS[rng.integers(0, 4, size=n)]
+    big[rng.random(n) < 0.0005] = ord("N")
+    big = big.tobytes()
+    queries, tasks = [], []
+    for a in (3, (1 << 16) - 150, (1 << 24) - 150, n - 300):
+        piece = big[a:a + 300]
+        queries.append(_substitute(rng, piece, 0.03) if a == n - 300 else ac.mutate(rng, piece, 0.03, 0.004))
+        tasks += [(len(queries) - 1, 1, a, 0), (len(queries), 1, a, 1)]
+        queries.append(ac.orient(queries[-1], 1))
+    tasks += [(4, 1, (1 << 24) - 150 + band, 0), (4, 1, (1 << 24) - 150 - band, 0), (6, 1, n - 300 + band, 0), (0, 1, 3 - band, 0), (1, 1, 3 - band, 1)]
+    m = len(queries[0])
+    tasks += [(0, 1, n + band, 0), (0, 1, -(m - 1) - band - 1, 0), (0, 1, n - 1 + band, 0), (0, 1, -(m - 1) - band, 1), (0, 0, 0, 0)]
+    got = _check(dev, queries, [b"ACGTACGTACGTA", big], tasks, band, "far diagonals")
+    score, rend = got[0].tolist(), got[4].tolist()
+    assert min(score[:8]) > 500 and rend[6] == rend[7] == n and score[13] == score[14] == 0 and rend[4] > 1 << 24
+
+
+def test_a_task_of_65536_rows_while_its_neighbours_stride_on(dev):
+    """more short tasks than the largest grid has waves, and among the first of them one that keeps its wave for 2^16 rows: the other
+    three waves of its workgroup go on to their next tasks meanwhile"""
+    rng = np.random.Generator(np.random.PCG64(65537))
+    band, nshort = 4, 4 * GRID_MAX + 3000
+    long_q = mc.random_record(rng, (1 << 16) + 200, 0.002)
+    long_r = mc.random_record(rng, 90) + ac.mutate(rng, long_q, 0.02, 0.0005) + mc.random_record(rng, 100)
+    q, r, tasks = _short_batch(rng, 3000, 2000, nshort)
+    records = lambda x: [x[0][int(a):int(b)].tobytes() for a, b in zip(x[1][:-1], x[1][1:])]
+    queries, refs = records(q) + [long_q], records(r) + [long_r]
+    short = list(zip(*(t.tolist() for t in tasks)))
+    want_short = ac.banded_batch(*q, *r, *tasks, band)
+    want_long = ac.banded(long_q, long_r, 90, band)
+    assert want_long[0] > 2 * (1 << 16) and want_long[2] > 1 << 16
+    where = 5
+    got = dev.run(queries, refs, short[:where] + [(3000, 2000, 90, 0)] + short[where:], band)
+    assert tuple(int(g[where]) for g in got) == want_long
+    _same([np.delete(g, where) for g in got], want_short, "short around 2^16 rows")
+    assert tuple(int(g[0]) for g in dev.run([long_q], [long_r], [(0, 0, 90, 0)], band)) == want_long
+
+
 # ---- refusals ----
 
 def _untouched(out):

@@ -196,6 +196,133 @@ def test_a_long_record_before_many_short_ones(dev):
     _check(dev, records[1:400] + records[:1] + records[400:800], k, w, False, mc.LEX, "short, long, short")
 
 
+# ---- the piece counts of whole read sets and contigs ----
+
+# scan_top_kernel takes the sums of the scan blocks SCAN_TPB at a time and carries the running sum from one trip to the next: a second
+# trip needs more than SCAN_TOP pieces in one call
+_SCAN = re.search(r"constexpr int SCAN_TPB = (\d+), SCAN_ITEMS = (\d+);", open(os.path.join(ROOT, "kmerdb_amd", "csrc", "kdb_minimizers.hip.h")).read())
+SCAN_TPB, SCAN_ITEMS = int(_SCAN.group(1)), int(_SCAN.group(2))
+SCAN_BLOCK = SCAN_TPB * SCAN_ITEMS
+SCAN_TOP = SCAN_TPB * SCAN_BLOCK
+SHORT_K, SHORT_W = 5, 4                                                       # a record of 8 residues has w start positions
+
+
+def _short_records(n, seed, quiet=()):
+    """n records of 8 .. 20 residues, a tenth of them empty, a twentieth all N, and none with a minimizer in the ranges `quiet`
+    -> (bases, offsets, lens, all_n)"""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    lens = rng.integers(8, 21, size=n)
+    kind = rng.integers(0, 20, size=n)
+    lens[kind < 2] = 0
+    for a, b in quiet:
+        lens[a:b:2] = 0                                                       # empty and all N by turns
+        kind[a:b] = 2
+    offsets = np.zeros(n + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum(lens)
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=int(offsets[-1]))].copy()
+    bases[rng.random(bases.size) < 0.02] = ord("N")
+    all_n = kind == 2
+    bases[np.repeat(all_n, lens)] = ord("N")
+    return bases, offsets, lens, all_n
+
+
+def _spot_check(bases, offsets, got, rows, k, w, canonical, order):
+    """the restatement proper on the records `rows` of a batch's output"""
+    counts, ids, pos, strand = got
+    ends = np.cumsum(counts.astype(np.int64))
+    raw = bases.tobytes()
+    for r in rows:
+        p, i, s = mc.record_minimizers(raw[int(offsets[r]):int(offsets[r + 1])], k, w, canonical, order)
+        e = int(ends[r])
+        assert int(counts[r]) == p.size and (pos[e - p.size:e].tolist(), ids[e - p.size:e].tolist(), strand[e - p.size:e].tolist()) == (p.tolist(), i.tolist(), s.tolist()), r
+
+
+@pytest.mark.parametrize("canonical,order", [(True, mc.HASHED), (False, mc.LEX)])
+@pytest.mark.parametrize("n", [SCAN_TOP, SCAN_TOP + 1, 2 * SCAN_TOP + 3])
+def test_one_two_and_three_trips_of_the_top_scan(dev, n, canonical, order):
+    """one piece per record: one trip exactly, a second trip of one block sum, three trips; more than a scan block of records without a
+    minimizer lies across piece SCAN_TOP (up to it where the call ends there)"""
+    quiet = (SCAN_TOP - SCAN_BLOCK - 100, min(n, SCAN_TOP + SCAN_BLOCK // 2 + 100))
+    bases, offsets, lens, all_n = _short_records(n, n, [quiet])
+    assert quiet[1] - quiet[0] > SCAN_BLOCK
+    rc, counts, ids, pos, strand, total = dev.raw(bases, offsets, SHORT_K, SHORT_W, 1 if canonical else 0, order)
+    assert rc == dev.OK
+    want = mc.batch_minimizers_flat(bases, offsets, SHORT_K, SHORT_W, canonical, order)
+    assert total == int(want[0].sum()) > n and total <= bases.size
+    got = (counts, ids[:total], pos[:total], strand[:total])
+    _same(got, want, ("top scan", n))
+    assert np.all(ids[total:] == FILL64) and np.all(pos[total:] == FILL32) and np.all(strand[total:] == FILL8)
+    assert not counts[lens == 0].any() and not counts[all_n].any() and not counts[quiet[0]:quiet[1]].any()
+    assert counts[quiet[0] - 50:quiet[0]].any() and (quiet[1] == n or counts[quiet[1]:quiet[1] + 50].any())
+    rows = [0, SCAN_BLOCK - 1, SCAN_BLOCK, quiet[0] - 1, SCAN_TOP - 2, SCAN_TOP - 1, SCAN_TOP, SCAN_TOP + 1, quiet[1], 2 * SCAN_TOP - 1, 2 * SCAN_TOP, n - 1]
+    _spot_check(bases, offsets, got, [r for r in rows if r < n], SHORT_K, SHORT_W, canonical, order)
+
+
+@pytest.mark.parametrize("canonical,order", [(True, mc.HASHED), (False, mc.LEX)])
+def test_records_of_several_pieces_in_a_call_of_two_trips(dev, canonical, order):
+    """piece_rec is there: a record of five pieces first, one whose four pieces are SCAN_TOP - 2 .. SCAN_TOP + 1, one of four last"""
+    k, w = SHORT_K, SHORT_W
+    rng = np.random.Generator(np.random.PCG64(2 * SCAN_TOP))
+    long = [np.frombuffer(mc.random_record(rng, mc.length_for(nwin, k), 0.001), dtype=np.uint8) for nwin in (5 * P, 3 * P + 1, 3 * P + 17)]
+    between, after = SCAN_TOP - 2 - 5, 1000
+    b1, o1, l1, _ = _short_records(between, 11)
+    b2, o2, l2, _ = _short_records(after, 12)
+    bases = np.concatenate([long[0], b1, long[1], b2, long[2]])
+    lens = np.concatenate([[long[0].size], l1, [long[1].size], l2, [long[2].size]])
+    offsets = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
+    nwin = np.maximum(lens - k + 1, 0)
+    first_piece = np.concatenate(([0], np.cumsum(np.maximum(1, -(-nwin // P)))))
+    at = between + 1                                                          # the record across piece SCAN_TOP
+    assert int(first_piece[at]) == SCAN_TOP - 2 and int(first_piece[at + 1]) == SCAN_TOP + 2 and int(first_piece[-1]) > SCAN_TOP + after
+    rc, counts, ids, pos, strand, total = dev.raw(bases, offsets, k, w, 1 if canonical else 0, order)
+    assert rc == dev.OK
+    want = mc.batch_minimizers_flat(bases, offsets, k, w, canonical, order)
+    assert total == int(want[0].sum())
+    got = (counts, ids[:total], pos[:total], strand[:total])
+    _same(got, want, "several pieces, two trips")
+    assert all(int(counts[r]) > nw // w for r, nw in ((0, 5 * P), (at, 3 * P + 1), (lens.size - 1, 3 * P + 17)))
+    _spot_check(bases, offsets, got, [0, 1, at - 1, at, at + 1, lens.size - 2, lens.size - 1], k, w, canonical, order)
+
+
+@pytest.mark.parametrize("k,w,pieces", [(15, 10, 2100), (31, 256, 300)])
+def test_one_record_of_more_pieces_than_a_scan_block(dev, k, w, pieces):
+    """a record's count is the difference of two prefix sums SCAN_BLOCK and more pieces apart (k = 15: over four megabases), and its
+    positions do not fit 22 bits; at w = 256 every piece reads a halo of 255 keys on either side"""
+    rng = np.random.Generator(np.random.PCG64(pieces))
+    nwin = pieces * P + 301
+    contig = bytearray(mc.random_record(rng, mc.length_for(nwin, k)))
+    for at in rng.integers(0, len(contig), size=9).tolist():
+        contig[at] = ord("N")
+    shorts = [mc.random_record(rng, int(n), 0.01) for n in rng.integers(0, 90, size=60)]
+    records = shorts[:35] + [bytes(contig)] + shorts[35:]
+    counts, ids, pos, strand = _check(dev, records, k, w, True, mc.HASHED, "a contig")
+    e = int(counts[:36].sum())
+    mine = pos[e - int(counts[35]):e].astype(np.int64)
+    assert (pieces <= SCAN_BLOCK or int(mine.max()) > 2 ** 22) and int(counts[35]) > nwin // w and np.all(np.diff(mine) > 0) and int(mine[-1]) >= nwin - w
+
+
+@pytest.mark.parametrize("order", [mc.LEX, mc.HASHED])
+@pytest.mark.parametrize("canonical", [False, True])
+def test_whole_pieces_without_a_key_inside_a_record(dev, canonical, order):
+    """Eight pieces: N from the record's start past its first two pieces, N over two pieces in its middle, and N from w - 1 positions
+    before the last piece to the end -- that piece selects nothing (emit_kernel leaves at once) and its left neighbour's halo is all
+    +infinity."""
+    rng = np.random.Generator(np.random.PCG64(88))
+    for k, w in [(15, 10), (5, 200), (31, 256)]:
+        L = mc.length_for(8 * P, k)
+        rec = bytearray(mc.random_record(rng, L))
+        rec[:2 * P + w + 5] = b"N" * (2 * P + w + 5)
+        rec[4 * P - 30:6 * P + w + 40] = b"N" * (2 * P + w + 70)
+        rec[7 * P - w:] = b"N" * (L - (7 * P - w))
+        middle = bytearray(mc.random_record(rng, mc.length_for(3 * P + 9, k)))   # only its middle piece has no key
+        middle[P - k + 1:2 * P + k - 1] = b"N" * (P + 2 * k - 2)
+        records = [mc.random_record(rng, 200), bytes(rec), b"N" * (2 * P + 50), mc.random_record(rng, 64), bytes(middle), b"", bytes(rec), mc.random_record(rng, 30)]
+        counts, ids, pos, strand = _check(dev, records, k, w, canonical, order, "pieces of N")
+        mine = pos[int(counts[0]):int(counts[:2].sum())].astype(np.int64)
+        assert int(counts[2]) == 0 and int(counts[1]) == int(counts[6]) > 0
+        assert sorted(set((mine // P).tolist())) == [2, 3, 6] and int(mine[0]) == 2 * P + w + 5 and int(mine[-1]) == 7 * P - w - k
+
+
 # ---- capacity ----
 
 def test_capacity(dev):

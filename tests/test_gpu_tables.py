@@ -136,6 +136,98 @@ def test_seventy_thousand_records(dev):
         assert (tables[r].tolist(), int(windows[r]), int(skipped[r]), int(first[r]), int(last[r])) == (row.tolist(), w, s, fi, la)
 
 
+# ---- the piece and record counts of whole genomes ----
+
+def test_more_multi_piece_records_than_the_zeroing_grid_has_workgroups(dev):
+    """tables_zero_kernel is launched with at most 4096 workgroups and strides through the records of more than one piece: 4113 of them,
+    two pieces each, with single-piece and empty records in between so that they are no contiguous range of rows"""
+    nmulti, k = 4096 + 17, 2
+    L = tc.length_for(PIECE + 3, k, 1)
+    rng = np.random.Generator(np.random.PCG64(4113))
+    block = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, size=(nmulti, L))].copy()
+    block[rng.random((nmulti, L)) < 0.001] = ord("N")
+    block[5, :PIECE + 1] = ord("N")                                           # a first piece without a counted window
+    block[6, PIECE:] = ord("N")                                               # ... and a second one
+    block[7, :] = ord("N")
+    small = {i: np.frombuffer(tc.random_record(rng, int(rng.integers(k, 60)), 0.02), dtype=np.uint8) for i in range(0, nmulti, 3)}
+    empty = set(range(0, nmulti, 7))
+    parts, lens, rows_multi, rows_small = [], [], [], []
+    for i in range(nmulti):
+        rows_multi.append(len(lens))
+        parts.append(block[i])
+        lens.append(L)
+        if i in small:
+            rows_small.append(len(lens))
+            parts.append(small[i])
+            lens.append(small[i].size)
+        if i in empty:
+            lens.append(0)
+    offsets = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
+    bases = np.concatenate(parts)
+    n = len(lens)
+    assert bases.size == int(offsets[-1]) and nmulti > 4096 and rows_multi[-1] - rows_multi[0] + 1 > nmulti
+    want = [np.zeros((n, 4 ** k), dtype=np.uint32), np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64), np.full(n, -1, dtype=np.int32), np.full(n, -1, dtype=np.int32)]
+    for w, u in zip(want, tc.uniform_tables(block, k)):
+        w[rows_multi] = u
+    for w, u in zip(want, tc.batch_tables([small[i].tobytes() for i in sorted(small)], k)):
+        w[rows_small] = u
+    # The same shapes first as poly-T: where the allocator hands the second call the first one's block, the rows that have to be zeroed hold
+    # PIECE + 3 in their last entry then.  Best effort: nothing here can tell whether the block was reused, and nothing asserts it.
+    stale = np.where(bases == ord("N"), bases, np.uint8(ord("T")))
+    rc, (tables, windows, skipped, first, last) = dev.raw(stale, offsets, k, 1)
+    assert rc == dev.OK and int(tables[rows_multi[0]][15]) == PIECE + 3 - int(skipped[rows_multi[0]]) and not tables[:, :15].any()
+    rc, got = dev.raw(bases, offsets, k, 1)
+    assert rc == dev.OK
+    for name, g, w in zip(("tables", "windows", "skipped", "first_id", "last_id"), got, want):
+        assert g.dtype == w.dtype and g.shape == w.shape, name
+        assert g.tobytes() == w.tobytes(), (name, np.argwhere(g != w)[:8].tolist())
+    assert 0 < int(got[1][rows_multi[5]]) <= 2 and int(got[3][rows_multi[5]]) >= 0 and int(got[4][rows_multi[6]]) >= 0
+    assert [int(g[rows_multi[7]]) for g in got[1:]] == [0, PIECE + 3, -1, -1] and not got[0][rows_multi[7]].any()
+    for r in (rows_multi[0], rows_multi[5], rows_multi[6], rows_multi[7], rows_multi[4095], rows_multi[4096], rows_multi[4097], rows_multi[-1], n - 1):
+        row, w, s, fi, la = tc.record_table(bases[int(offsets[r]):int(offsets[r + 1])].tobytes(), k)       # (the restatement proper, on a few)
+        assert (got[0][r].tolist(), int(got[1][r]), int(got[2][r]), int(got[3][r]), int(got[4][r])) == (row.tolist(), w, s, fi, la), r
+
+
+@pytest.mark.parametrize("canonical", [False, True])
+@pytest.mark.parametrize("k,stride", [(1, 1), (3, 3), (6, 1), (6, 6)])
+def test_a_record_of_a_hundred_and_fifty_pieces(dev, k, stride, canonical):
+    """a contig of more than a megabase: every entry of its row is added to by the waves of 150 pieces"""
+    rng = np.random.Generator(np.random.PCG64(150 * k + stride))
+    nwin = 150 * PIECE + 77
+    contig = bytearray(tc.random_record(rng, tc.length_for(nwin, k, stride) + stride - 1))
+    for at in rng.integers(0, len(contig), size=12).tolist():
+        contig[at] = ord("N")
+    records = [tc.random_record(rng, 50, 0.02), b"", bytes(contig), tc.random_record(rng, k), tc.random_record(rng, tc.length_for(PIECE + 1, k, stride)), b"N" * 40]
+    tables, windows, skipped, first, last = _check(dev, records, k, stride, canonical, name="150 pieces")
+    assert int(windows[2] + skipped[2]) == nwin > 150 * PIECE and 0 < int(skipped[2]) <= 12 * k
+    assert int(tables[2].sum(dtype=np.uint64)) == int(windows[2]) and int(tables.sum(dtype=np.uint64)) == int(windows.sum())
+
+
+@pytest.mark.parametrize("k,stride,canonical", [(3, 3, True), (4, 1, False), (6, 3, True), (1, 1, False), (2, 1, True)])
+def test_pieces_without_a_counted_window_at_a_records_ends(dev, k, stride, canonical):
+    """tables_record_kernel joins the pieces' first and last ids in piece order and passes over a piece that reports -1: a record whose
+    pieces 0, 1 and 4 of five are all N has both from its interior, and one that is N over three pieces has neither"""
+    rng = np.random.Generator(np.random.PCG64(31 * k + stride))
+    L = tc.length_for(5 * PIECE, k, stride)
+    rec = bytearray(tc.random_record(rng, L))
+    rec[:2 * PIECE * stride] = b"N" * (2 * PIECE * stride)                   # the windows 0 .. 2 PIECE - 1 begin with an N
+    rec[4 * PIECE * stride:] = b"N" * (L - 4 * PIECE * stride)                # ... and so do those from 4 PIECE on
+    inner = bytearray(tc.random_record(rng, L))                               # the mirror: only the pieces 0 and 4 count anything
+    inner[PIECE * stride:4 * PIECE * stride] = b"N" * (3 * PIECE * stride)
+    all_n = b"N" * tc.length_for(2 * PIECE + 5, k, stride)
+    records = [tc.random_record(rng, 70), bytes(rec), all_n, b"", bytes(inner), tc.random_record(rng, 33, 0.1), all_n, bytes(rec)]
+    tables, windows, skipped, first, last = _check(dev, records, k, stride, canonical, name="pieces of N")
+    assert int(windows[1] + skipped[1]) == 5 * PIECE and 2 * PIECE - k < int(windows[1]) <= 2 * PIECE and int(first[1]) >= 0 and int(last[1]) >= 0
+    assert (int(windows[2]), int(skipped[2]), int(first[2]), int(last[2])) == (0, 2 * PIECE + 5, -1, -1) and not tables[2].any()
+    assert int(skipped[4]) >= 3 * PIECE and int(first[4]) >= 0 and int(last[4]) >= 0
+    for r in (1, 4):                                                          # the ids are those of the first and last window without an N
+        s = records[r]
+        starts = [p for p in tc.window_starts(len(s), k, stride).tolist() if b"N" not in s[p:p + k]]
+        ids = [int(tc.record_table(s[p:p + k], k, 1, canonical)[3]) for p in (starts[0], starts[-1])]
+        assert (int(first[r]), int(last[r])) == tuple(ids), r
+        assert (2 * PIECE <= starts[0] // stride < 3 * PIECE and starts[-1] // stride < 4 * PIECE) if r == 1 else (starts[0] == 0 and starts[-1] // stride >= 4 * PIECE)
+
+
 def test_a_records_row_does_not_depend_on_the_batch(dev):
     k, stride = 5, 2
     records = tc.ladder_records(k, stride, PIECE, 9)

@@ -74,6 +74,23 @@ def test_restatement_and_host_rules_reproduce_the_reference_list(golden, sequenc
     assert "length" in seen and {("flag", False, 0), ("flag", True, 0), ("flag", True, 1), ("flag", True, 2), ("flag", True, 3)} <= seen
 
 
+@pytest.mark.parametrize("canonical", [False, True])
+@pytest.mark.parametrize("k,stride", [(1, 1), (2, 1), (3, 3), (4, 2), (6, 1), (6, 6)])
+def test_uniform_tables_equals_the_per_record_restatement(k, stride, canonical):
+    """tc.uniform_tables, the vectorised form the GPU tests use for thousands of records of one length, against tc.record_table"""
+    rng = np.random.Generator(np.random.PCG64(1000 * k + 10 * stride + canonical))
+    for length in (0, k - 1, k, k + stride, 37, 64):
+        recs = [tc.random_record(rng, length, p) for p in (0.0, 0.0, 0.05, 0.3, 0.3)] + [b"N" * length, b"T" * length]
+        if length >= 2 * k + 1:
+            recs += [b"N" * k + recs[0][k:], recs[1][:-k] + b"N" * k, b"N" * (length - k) + recs[0][:k]]      # no first window, no last one, only the last
+        block = np.frombuffer(b"".join(recs), dtype=np.uint8).reshape(len(recs), length)
+        got, want = tc.uniform_tables(block, k, stride, canonical), tc.batch_tables(recs, k, stride, canonical)
+        for g, x in zip(got, want):
+            assert g.dtype == x.dtype and g.shape == x.shape and g.tobytes() == x.tobytes(), (length, g.tolist(), x.tolist())
+    with pytest.raises(ValueError):
+        tc.uniform_tables(np.frombuffer(b"ACGTRACG", dtype=np.uint8).reshape(2, 4), 2)
+
+
 def test_codon_frequency_table_as_reference_equals_the_reference(golden, sequences, stubbed):
     codons, _ = stubbed
     raised = returned = 0
