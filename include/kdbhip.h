@@ -283,10 +283,14 @@ int kdb_scale_counts(int device_id, const void *d_vector, uint64_t nbins, double
  * table and the number alone, otherwise it holds over_cap entries (KDB_ERR_ARG if fewer than *n_over_out, with *n_over_out and the
  * table set).  KDB_ERR_ARG: a NULL or misaligned pointer, nbins == 0 or above 2^36.  KDB_ERR_NOMEM: the scratch does not fit.
  * kernel_ms_out (may be NULL): device time of the sweep, by HIP events.
- * KDB_SPECTRUM_WG_BINS: bins one workgroup of either kernel covers per grid stride.
+ * KDB_SPECTRUM_WG_BINS: bins one workgroup of either kernel covers per grid stride.  KDB_SPECTRUM_GRID_MAX: the most workgroups of
+ * either kernel, so one grid stride is KDB_SPECTRUM_GRID_MAX x KDB_SPECTRUM_WG_BINS bins.  KDB_SPECTRUM_LIST_GUESS: the values
+ * >= KDB_SPECTRUM_DENSE that kdb_rank_transform's first sweep has room for; a vector with more of them is swept a second time.
  */
 #define KDB_SPECTRUM_DENSE 65536
 #define KDB_SPECTRUM_WG_BINS 1024
+#define KDB_SPECTRUM_GRID_MAX 1024
+#define KDB_SPECTRUM_LIST_GUESS 1048576
 int kdb_spectrum(int device_id, const void *d_vector, uint64_t nbins,
                  uint64_t *dense_out       /* KDB_SPECTRUM_DENSE words */,
                  uint64_t *over_values_out /* may be NULL */, uint64_t over_cap, uint64_t *n_over_out,

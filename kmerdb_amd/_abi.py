@@ -20,6 +20,7 @@ KDB_N_KERNELS = 8
 KDB_GRAM_MAX, KDB_GRAM_BLOCK, KDB_GRAM_WG_BINS = 64, 4, 512
 KDB_GRAM_GRID_MAX, KDB_GRAM_GRID_MAX_MANY_ROWS, KDB_GRAM_GRID_MANY_ROWS = 1024, 256, 4
 KDB_SPECTRUM_DENSE, KDB_SPECTRUM_WG_BINS = 65536, 1024
+KDB_SPECTRUM_GRID_MAX, KDB_SPECTRUM_LIST_GUESS = 1024, 1 << 20
 KDB_PAIRSTATS_BLOCK, KDB_PAIRSTATS_HALF, KDB_PAIRSTATS_WG_BINS = 4, 2, 512
 KDB_PAIRFLOAT_GRID_MAX = 512
 KDB_SIZEFACTORS_WG_BINS, KDB_SIZEFACTORS_GRID_MAX = 512, 1024

@@ -521,7 +521,7 @@ int kdb_rank_transform(int device_id, const void *d_vector, uint64_t nbins, void
     SpectrumScratch sc;
     std::vector<uint64_t> host;
     // the list is short on count profiles (at most Sum counts / 65536 values): a first guess, and a second sweep with the exact length where it was wrong
-    if (int rc = spectrum_alloc("kdb_rank_transform", call, sc, std::min<uint64_t>(nbins, 1u << 20))) return rc;
+    if (int rc = spectrum_alloc("kdb_rank_transform", call, sc, std::min<uint64_t>(nbins, KDB_SPECTRUM_LIST_GUESS))) return rc;
     if (int rc = spectrum_sweep(call, sc, d_vector, nbins, host)) return rc;
     if (host[kdbspectrum::DENSE] > sc.cap) {
         if (int rc = spectrum_alloc("kdb_rank_transform", call, sc, host[kdbspectrum::DENSE])) return rc;

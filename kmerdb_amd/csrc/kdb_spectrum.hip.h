@@ -40,7 +40,7 @@ constexpr int WG_BINS = (TPB / 64) * CHUNK_BINS;   // bins one workgroup covers 
 constexpr uint32_t NPRIV = 16;                     // values with a counter per lane: 16 x 256 x 4 bytes = 16 KiB of LDS
 constexpr uint32_t LDS_BINS = 4096;                // values with a counter per workgroup: another 16 KiB
 constexpr uint32_t RANK_LDS = 2048;                // rank_map_kernel: entries of the dense rank table kept in LDS (16 KiB)
-constexpr uint32_t MAX_GRID = 1024;                // workgroups of either kernel: four per CU
+constexpr uint32_t MAX_GRID = KDB_SPECTRUM_GRID_MAX;   // workgroups of either kernel: four per CU
 constexpr uint64_t MAX_BINS = 1ull << 36;          // what the entry points accept
 static_assert(DENSE == 65536 && WG_BINS == KDB_SPECTRUM_WG_BINS, "include/kdbhip.h states the kernel's constants");
 static_assert(NPRIV <= LDS_BINS && LDS_BINS <= DENSE && RANK_LDS <= DENSE, "the tiers nest");

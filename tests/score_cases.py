@@ -254,3 +254,46 @@ def accuracy_cases(piece):
     cases.append(("four bins at the top under a pseudocount, k=3", k, False, v, TOP - 64 * 5, 5, records))
     assert len(cases) == N_ACCURACY_CASES
     return cases
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the decode's edges at k = 14 .. 17: the last of the five 32-bit words a window arrives in, at every byte alignment
+# ---------------------------------------------------------------------------------------------------------------
+_NEXT = {"A": "C", "C": "G", "G": "T", "T": "A"}
+DECODE_EDGE_ROLES = ("alone", "last", "r13", "r12", "n_after", "n_last", "n_after_more", "inside", "ends_buffer")
+
+
+def decode_edge_kmers(k):
+    """{name: k-mer}: K ends in T behind eight residues that are not T (so no residue 1 .. 7 places before the last equals the last);
+    `last`, `r13`, `r12`: K with its last residue, residue 13 and residue 12 (from 0) replaced -- at k = 14 residue 13 is the last"""
+    assert 14 <= k <= 17
+    K = "TGCATGCA"[:k - 9] + "CAGGACGA" + "T"
+    swap = lambda s, i: s[:i] + _NEXT[s[i]] + s[i + 1:]
+    return {"K": K, "last": swap(K, k - 1), "r13": swap(K, 13), "r12": swap(K, 12)}
+
+
+def decode_edge_records(k, alignment, seed=0, start=0):
+    """-> (records, {role: index of its record}): every record with a role starts at a byte offset of the packed buffer that is
+    `alignment` modulo 8 (a filler record before each sees to that; `start`: the bytes of the records a caller packs before these), and
+    its window of interest is the one at its start:
+        alone, last, r13, r12   the k-mers of decode_edge_kmers, one window each
+        n_after                 K N: the N lies one past the window's end, the window is scored (and the next one is not)
+        n_last                  K with N for its last residue: no window
+        n_after_more            K N K: two scored windows around k that are not
+        inside                  K `last` K: the three k-mers and the junk between them, at every alignment from here on
+        ends_buffer             K as the last record of the buffer: its window ends where the buffer does"""
+    rng = np.random.default_rng(1000 * k + 10 * alignment + seed)
+    kmers = decode_edge_kmers(k)
+    K = kmers["K"]
+    body = {"alone": K, "last": kmers["last"], "r13": kmers["r13"], "r12": kmers["r12"], "n_after": K + "N", "n_last": K[:-1] + "N",
+            "n_after_more": K + "N" + K, "inside": K + kmers["last"] + K, "ends_buffer": K}
+    records, roles, at = [], {}, start
+    for role in DECODE_EDGE_ROLES:
+        n = k + (alignment - at - k) % 8
+        records.append(random_record(rng, n))
+        at += n
+        assert at % 8 == alignment
+        roles[role] = len(records)
+        records.append(body[role].encode())
+        at += len(body[role])
+    return records, roles

@@ -208,6 +208,61 @@ def test_ids_above_2_31_and_byte_offsets_above_2_32_at_k16(dev):
     torch.cuda.empty_cache()
 
 
+@pytest.mark.parametrize("k", [14, 15, 17])
+def test_the_decode_at_k_14_15_17_at_every_byte_alignment(dev, k):
+    """window_id's fourth and fifth word: m[3] covers two (k = 14) and three (k = 15) bytes, and k = 17 alone uses m[4] and
+    x[4] = w[2] >> s, of which it needs the one byte that has no word behind it.  The vectors are 2 GiB, 8 GiB and 128 GiB, zero but for
+    a few bins.  Per alignment of the window's start: k-mers that differ in their last residue, in residue 13 and in residue 12 hold
+    different counts; an N one past the window's end leaves the window scored, an N as its last residue does not; the last record ends
+    where the buffer does."""
+    import torch
+    try:
+        t = torch.zeros(4 ** k, dtype=torch.int64, device="cuda:0")
+    except (RuntimeError, MemoryError) as e:
+        pytest.skip("no room for the {0} GiB vector of k = {1}: {2}".format(4 ** k * 8 // 2 ** 30, k, e))
+    try:
+        kmers = sc.decode_edge_kmers(k)
+        corners = [("ACGT" * 5)[:k], "C" + "A" * (k - 1), "G" + "T" * (k - 1), "T" * k, "T" * (k - 1) + "G", "A" * k]
+        ids = []
+        for x in list(kmers.values()) + corners:                             # the k-mers and their reverse complements: canonical lookups differ too
+            for i in (sc.kmer_id(x), sc.rc_id(sc.kmer_id(x), k)):
+                if i not in ids:
+                    ids.append(i)
+        if k == 17:
+            assert sum(i >= 2 ** 32 for i in ids) >= 4 and sum(i * 8 >= 2 ** 36 for i in ids) >= 4
+        sparse = {i: 3 + 5 * n for n, i in enumerate(ids)}
+        t[torch.tensor(ids, device="cuda:0")] = torch.tensor([sparse[i] for i in ids], dtype=torch.int64, device="cuda:0")
+        total = sum(sparse.values())
+
+        class Sparse:                                                        # the oracle's view of the vector: zeros but for the set bins
+            def __len__(self):
+                return 4 ** k
+
+            def __getitem__(self, i):
+                return sparse.get(int(i), 0)
+
+        count = {name: sparse[sc.kmer_id(x)] for name, x in kmers.items()}
+        assert len(set(count.values())) == (3 if k == 14 else 4)
+        for alignment in range(8):
+            records, roles = sc.decode_edge_records(k, alignment, start=len(corners) * k)
+            records = [x.encode() for x in corners] + records
+            _, offsets = sc.pack(records)
+            at = {role: i + len(corners) for role, i in roles.items()}
+            assert all(int(offsets[i]) % 8 == alignment for i in at.values()) and at["ends_buffer"] == len(records) - 1
+            for canonical in (False, True):
+                got = _check_batch(dev, records, Sparse(), t, k, canonical, total, 1, name="k=%d alignment %d" % (k, alignment))
+                log10_p, windows, zeros, mins = got
+                assert [int(windows[at[r]]) for r in sc.DECODE_EDGE_ROLES] == [1, 1, 1, 1, 1, 0, 2, 2 * k + 1, 1]
+                assert math.isnan(log10_p[at["n_last"]]) and np.all(np.isfinite(np.delete(log10_p, at["n_last"])))
+                if not canonical:
+                    assert [int(mins[at[r]]) for r in ("alone", "last", "r13", "r12", "n_after", "n_after_more", "ends_buffer")] == \
+                        [count["K"], count["last"], count["r13"], count["r12"], count["K"], count["K"], count["K"]]
+                    assert int(zeros[at["inside"]]) == 2 * k + 1 - 3 and int(zeros[at["n_after_more"]]) == 0
+    finally:
+        del t
+        torch.cuda.empty_cache()
+
+
 # ---- KDB_SCORE_CONTINUES ----
 
 @pytest.mark.parametrize("k", [1, 4, 9])

@@ -215,3 +215,37 @@ def test_the_probability_subcommand_parses_the_references_positionals():
         with pytest.raises(SystemExit):
             ap.parse_args(bad)
     assert ap.parse_args(["spectrum", "a.kdb"]).cmd == "spectrum"            # (the other subcommands are where they were)
+
+
+# ---- the records of the decode's edges (k = 14 .. 17) ----
+
+@pytest.mark.parametrize("k", [14, 15, 16, 17])
+def test_decode_edge_records_are_where_they_claim_to_be(k):
+    kmers = sc.decode_edge_kmers(k)
+    K = kmers["K"]
+    ids = {name: sc.kmer_id(x) for name, x in kmers.items()}
+    assert len(K) == k and K[-1] == "T" and "T" not in K[-9:-1]
+    assert ids["K"] ^ ids["last"] in (1, 2, 3)                               # the last residue alone
+    assert (ids["K"] ^ ids["r13"]) >> (2 * (k - 14)) in (1, 2, 3) and (ids["K"] ^ ids["r12"]) >> (2 * (k - 13)) in (1, 2, 3)
+    assert (kmers["r13"] == kmers["last"]) == (k == 14) and len(set(ids.values())) == (3 if k == 14 else 4)
+
+    class Sparse:
+        def __len__(self):
+            return 4 ** k
+
+        def __getitem__(self, i):
+            return {ids["K"]: 3, ids["last"]: 8, ids["r13"]: 13 if k > 14 else 8, ids["r12"]: 18}.get(int(i), 0)
+
+    for alignment in range(8):
+        records, roles = sc.decode_edge_records(k, alignment)
+        bases, offsets = sc.pack(records)
+        assert sorted(roles) == sorted(sc.DECODE_EDGE_ROLES) and len(records) == 2 * len(roles)
+        assert all(int(offsets[i]) % 8 == alignment for i in roles.values())
+        assert roles["ends_buffer"] == len(records) - 1 and int(offsets[-1]) == bases.size == int(offsets[roles["ends_buffer"]]) + k
+        assert all(len(records[i - 1]) >= k and b"N" not in records[i - 1] for i in roles.values())
+        s = {role: sc.score_record(records[i], Sparse(), k, False, 42, 1) for role, i in roles.items()}
+        assert [s[r].windows for r in sc.DECODE_EDGE_ROLES] == [1, 1, 1, 1, 1, 0, 2, 2 * k + 1, 1]
+        assert [s[r].min_count for r in ("alone", "last", "r13", "r12", "n_after", "ends_buffer")] == [3, 8, 13 if k > 14 else 8, 18, 3, 3]
+        assert s["n_last"].log10_p is None and s["n_after_more"].all_windows == k + 2 and s["inside"].min_count == 0
+        # the window starts of `inside` pass through all eight alignments
+        assert {(int(offsets[roles["inside"]]) + p) % 8 for p in range(2 * k + 1)} == set(range(8))
