@@ -11,11 +11,10 @@ import sys
 
 import numpy as np
 
-from . import _abi
+from . import _abi, _records
 
 MAX_K = _abi.KDB_TABLES_MAX_K
 MAX_CALL_ENTRIES = 1 << 26                 # table entries (records x 4^k) tables_file asks of one call: 256 MiB of uint32
-_MAX_RESIDUES = 1 << 30                    # per kdb_record_tables call
 _MAX_ENTRIES = 1 << 31
 
 
@@ -33,21 +32,6 @@ def _check_scalars(k, stride, phase, continues):
     if phase and not continues:
         raise ValueError("kmerdb_amd.composition: a phase is for a record that continues the previous call's last one")
     return k, stride, phase
-
-
-def _check_batch(bases, offsets):
-    if isinstance(bases, (bytes, bytearray, memoryview)):
-        bases = np.frombuffer(bases, dtype=np.uint8)
-    if not isinstance(bases, np.ndarray) or bases.dtype != np.uint8 or bases.ndim != 1:
-        raise TypeError("kmerdb_amd.composition: bases must be bytes or a one-dimensional uint8 array")
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    if offsets.ndim != 1 or offsets.size < 1:
-        raise ValueError("kmerdb_amd.composition: offsets must hold nreads + 1 entries")
-    if int(offsets[0]) != 0 or int(offsets[-1]) != bases.size or np.any(offsets[1:] < offsets[:-1]):
-        raise ValueError("read_offsets must rise from 0 to nbytes")
-    if bases.size > _MAX_RESIDUES:
-        raise ValueError("kmerdb_amd.composition: at most 2^30 residues per call")
-    return np.ascontiguousarray(bases), offsets
 
 
 def record_tables_raw(bases, offsets, k, stride, canonical, phase, continues, device=0):
@@ -74,7 +58,7 @@ def record_tables(bases, offsets, k, stride=1, canonical=False, phase=0, continu
     residues, and its first window starts at `phase` (KDB_TABLES_CONTINUES).  A record shorter than k is a row of zeros.
     ValueError for what the call refuses: a residue outside upper-case ACGTN, more than 2^31 table entries."""
     k, stride, phase = _check_scalars(k, stride, phase, continues)
-    bases, offsets = _check_batch(bases, offsets)
+    bases, offsets = _records.check_batch("composition", bases, offsets)
     if (int(offsets.size) - 1) * 4 ** k > _MAX_ENTRIES:
         raise ValueError("kmerdb_amd.composition: more than 2^31 table entries (records x 4^k) in one call")
     from .distance import _require_device

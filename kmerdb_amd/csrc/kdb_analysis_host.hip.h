@@ -1,7 +1,9 @@
 // kdb_analysis_host.hip.h -- host side of the analysis calls of include/kdbhip.h, the ones that take finished vectors and no kdb_engine:
 // kdb_gram, kdb_pairstats, kdb_pairfloat, kdb_size_factors, kdb_scale_counts, kdb_spectrum, kdb_rank_transform, kdb_strand_merge,
 // kdb_score_reads, and kdb_record_tables, kdb_minimizers and kdb_align_banded (which take residues alone).  Every call works in an AnalysisCall: its own stream, events and
-// scratch, gone when it returns.  What the host alone decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.
+// scratch, gone when it returns.  What the host alone decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.  The three calls that
+// take residues and record offsets (kdb_score_reads, kdb_record_tables, kdb_minimizers) check them with record_check_args / record_check_sizes
+// and bring them and their kdbplan::RecordLayout to the device through one RecordBatch; kdb_align_banded stages its word-padded buffers itself.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -212,6 +214,56 @@ uint64_t residues_outside_acgtn(const uint8_t *bases, size_t nbytes)
     }
     return nbad;
 }
+
+// ---- what kdb_score_reads, kdb_record_tables and kdb_minimizers share: nbytes residues, the nreads + 1 offsets of their records ----
+
+// The batch's buffers; outputs: none of the call's own output arrays is NULL.  A batch without records passes: the caller answers it.
+int record_check_args(const char *who, const uint8_t *bases, size_t nbytes, const uint64_t *offs, size_t nreads, bool outputs)
+{
+    if (nreads == 0) return nbytes == 0 ? KDB_OK : fail(KDB_ERR_ARG, "%s: residues but no records", who);
+    if (!offs || (!bases && nbytes) || !outputs) return fail(KDB_ERR_ARG, "%s: NULL buffer", who);
+    return KDB_OK;
+}
+
+// the sizes the layout counts on: its piece indices then stay below 2^31
+int record_check_sizes(const char *who, size_t nbytes, size_t nreads)
+{
+    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "%s: at most 2^30 residues per call", who);
+    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "%s: at most 2^30 records per call", who);
+    return KDB_OK;
+}
+
+// the refusal of offsets that kdbplan::check_offsets() did not pass
+int record_offsets_fail(kdbplan::LayoutError bad)
+{
+    return fail(KDB_ERR_ARG, bad == kdbplan::LAYOUT_ENDS ? "read_offsets must start at 0 and end at nbytes" : "read_offsets must rise from 0 to nbytes");
+}
+
+// The batch on the device: the residues -- whole 16-byte lines and `pad` bytes more, for the aligned words the kernels read past a window's
+// start --, the offsets and the two arrays of the layout; piece_rec stays null where the layout has none.
+struct RecordBatch {
+    uint8_t *bases = nullptr;
+    uint64_t *offs = nullptr;
+    uint32_t *rec_piece0 = nullptr, *piece_rec = nullptr;
+
+    // false: no room for one of them
+    bool alloc(AnalysisCall &call, size_t nbytes, size_t nreads, const kdbplan::RecordLayout &lay, size_t pad)
+    {
+        bases = call.alloc<uint8_t>(((nbytes + 15) & ~(size_t)15) + pad);
+        offs = call.alloc<uint64_t>(nreads + 1);
+        rec_piece0 = call.alloc<uint32_t>(nreads + 1);
+        if (!lay.piece_rec.empty()) piece_rec = call.alloc<uint32_t>(lay.npieces);
+        return bases && offs && rec_piece0 && (lay.piece_rec.empty() || piece_rec);
+    }
+    int upload(AnalysisCall &call, const uint8_t *h_bases, size_t nbytes, const uint64_t *h_offs, size_t nreads, const kdbplan::RecordLayout &lay)
+    {
+        if (nbytes) HIP_TRY(hipMemcpyAsync(bases, h_bases, nbytes, hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(offs, h_offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(rec_piece0, lay.rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+        if (piece_rec) HIP_TRY(hipMemcpyAsync(piece_rec, lay.piece_rec.data(), lay.npieces * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+        return KDB_OK;
+    }
+};
 
 }  // namespace
 
@@ -582,48 +634,42 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
     const unsigned __int128 total2 = (unsigned __int128)total + (unsigned __int128)pseudocount * nbins;
     if ((total2 >> 64) != 0 || pseudocount >= (1ull << 62))
         return fail(KDB_ERR_ARG, "kdb_score_reads: total + pseudocount * 4^k and 4 * pseudocount must stay below 2^64");
-    if (nreads == 0) return nbytes == 0 ? KDB_OK : fail(KDB_ERR_ARG, "kdb_score_reads: residues but no records");
-    if (!offs || (!bases && nbytes) || !log10_p_out || !windows_out || !zero_windows_out || !min_count_out) return fail(KDB_ERR_ARG, "kdb_score_reads: NULL buffer");
-    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_score_reads: at most 2^30 residues per call");
-    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_score_reads: at most 2^30 records per call");
+    if (int rc = record_check_args("kdb_score_reads", bases, nbytes, offs, nreads, log10_p_out && windows_out && zero_windows_out && min_count_out)) return rc;
+    if (nreads == 0) return KDB_OK;
+    if (int rc = record_check_sizes("kdb_score_reads", nbytes, nreads)) return rc;
     const bool continues = (flags & KDB_SCORE_CONTINUES) != 0;
     // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
     kdbplan::ScoreLayout lay;
-    if (const kdbplan::LayoutError bad = kdbplan::score_layout(offs, nreads, nbytes, k, kdbscore::PIECE, continues, lay))
-        return fail(KDB_ERR_ARG, bad == kdbplan::LAYOUT_ENDS ? "read_offsets must start at 0 and end at nbytes" : "read_offsets must rise from 0 to nbytes");
+    if (const kdbplan::LayoutError bad = kdbplan::score_layout(offs, nreads, nbytes, k, kdbscore::PIECE, continues, lay)) return record_offsets_fail(bad);
     if (lay.nshort) return fail(KDB_ERR_SHORT_READ, "%llu record(s) shorter than k=%d (reference: kmer.py:461-463 raises)", (unsigned long long)lay.nshort, k);
     const uint64_t npieces = lay.npieces;
     AnalysisCall call;
     if (int rc = call.open(device_id)) return rc;
 
-    auto *d_bases = call.alloc<uint8_t>(((nbytes + 15) & ~(size_t)15) + 32);           // (piece_kernel's aligned words reach 23 bytes past a window's start)
-    auto *d_offs = call.alloc<uint64_t>(nreads + 1);
-    auto *rec_piece0 = call.alloc<uint32_t>(nreads + 1), *piece_rec = lay.piece_rec.empty() ? nullptr : call.alloc<uint32_t>(npieces);
+    RecordBatch in;
+    const bool staged = in.alloc(call, nbytes, nreads, lay, 32);                       // (piece_kernel's aligned words reach 23 bytes past a window's start)
     auto *pieces = call.alloc<kdbscore::PieceOut>(npieces);
     auto *ctr = call.alloc<kdb::DevCounters>(1);
     auto *log10_p = call.alloc<double>(nreads);
     auto *ints = call.alloc<unsigned long long>(3 * nreads);
-    if (!d_bases || !d_offs || !rec_piece0 || (!lay.piece_rec.empty() && !piece_rec) || !pieces || !ctr || !log10_p || !ints)
+    if (!staged || !pieces || !ctr || !log10_p || !ints)
         return fail(KDB_ERR_NOMEM, "kdb_score_reads: no room for the scratch of %zu residues in %zu records", nbytes, nreads);
     kdb::DevCounters c;
     memset(&c, 0, sizeof c);
     c.sus_count = 1;                       // more than sus_cap = 0: resolve_suspects_kernel judges every residue of the batch itself
-    if (nbytes) HIP_TRY(hipMemcpyAsync(d_bases, bases, nbytes, hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(rec_piece0, lay.rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    if (piece_rec) HIP_TRY(hipMemcpyAsync(piece_rec, lay.piece_rec.data(), npieces * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    if (int rc = in.upload(call, bases, nbytes, offs, nreads, lay)) return rc;
     HIP_TRY(hipMemcpyAsync(ctr, &c, sizeof c, hipMemcpyHostToDevice, call.st));
     HIP_TRY(call.begin());
     // what kdb_window_ids refuses: bytes with bit 7 set, letters outside ACGTN that no N shields (kmer.py:309 / :170)
-    hipLaunchKernelGGL(kdb::hibit_check_kernel, dim3(1024), dim3(256), 0, call.st, (const uint8_t *)d_bases, (uint64_t)nbytes, ctr);
+    hipLaunchKernelGGL(kdb::hibit_check_kernel, dim3(1024), dim3(256), 0, call.st, (const uint8_t *)in.bases, (uint64_t)nbytes, ctr);
     const unsigned check_grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(2048, (nbytes / 64 + 255) / 256));
-    hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(check_grid), dim3(256), 0, call.st, (const uint8_t *)d_bases, (uint64_t)nbytes, (const uint64_t *)d_offs,
+    hipLaunchKernelGGL(kdb::resolve_suspects_kernel, dim3(check_grid), dim3(256), 0, call.st, (const uint8_t *)in.bases, (uint64_t)nbytes, (const uint64_t *)in.offs,
                        (uint64_t)nreads, k, ctr, 0);
     hipLaunchKernelGGL(kdbscore::piece_kernel, dim3((unsigned)((npieces + kdbscore::TPB / 64 - 1) / (kdbscore::TPB / 64))), dim3(kdbscore::TPB), 0, call.st,
-                       (const uint8_t *)d_bases, (const uint64_t *)d_offs, (const uint32_t *)piece_rec, (const uint32_t *)rec_piece0, (uint32_t)npieces,
+                       (const uint8_t *)in.bases, (const uint64_t *)in.offs, (const uint32_t *)in.piece_rec, (const uint32_t *)in.rec_piece0, (uint32_t)npieces,
                        (const unsigned long long *)d_vector, k, canonical ? 1 : 0, (unsigned long long)pseudocount, pieces);
     hipLaunchKernelGGL(kdbscore::record_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, call.st, (const kdbscore::PieceOut *)pieces,
-                       (const uint32_t *)rec_piece0, (uint64_t)nreads, (double)(uint64_t)total2, continues ? 1 : 0, log10_p, ints, ints + nreads, ints + 2 * nreads);
+                       (const uint32_t *)in.rec_piece0, (uint64_t)nreads, (double)(uint64_t)total2, continues ? 1 : 0, log10_p, ints, ints + nreads, ints + 2 * nreads);
     HIP_TRY(hipGetLastError());
     HIP_TRY(call.end());
     HIP_TRY(hipMemcpyAsync(&c, ctr, sizeof c, hipMemcpyDeviceToHost, call.st));
@@ -649,49 +695,40 @@ int kdb_record_tables(int device_id, int k, int stride, int canonical, uint64_t 
     const bool continues = (flags & KDB_TABLES_CONTINUES) != 0;
     if (phase >= (uint64_t)stride) return fail(KDB_ERR_ARG, "kdb_record_tables: phase=%llu must be below stride=%d", (unsigned long long)phase, stride);
     if (phase != 0 && !continues) return fail(KDB_ERR_ARG, "kdb_record_tables: a phase needs KDB_TABLES_CONTINUES");
-    if (nreads == 0) return nbytes == 0 ? KDB_OK : fail(KDB_ERR_ARG, "kdb_record_tables: residues but no records");
-    if (!offs || (!bases && nbytes) || !tables_out || !windows_out || !skipped_out || !first_id_out || !last_id_out)
-        return fail(KDB_ERR_ARG, "kdb_record_tables: NULL buffer");
-    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_record_tables: at most 2^30 residues per call");
-    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_record_tables: at most 2^30 records per call");
+    if (int rc = record_check_args("kdb_record_tables", bases, nbytes, offs, nreads, tables_out && windows_out && skipped_out && first_id_out && last_id_out)) return rc;
+    if (nreads == 0) return KDB_OK;
+    if (int rc = record_check_sizes("kdb_record_tables", nbytes, nreads)) return rc;
     // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
     kdbplan::TablesLayout lay;
     if (const kdbplan::LayoutError bad = kdbplan::tables_layout(offs, nreads, nbytes, k, stride, phase, kdbtables::PIECE, 1ull << 31, lay))
-        return fail(KDB_ERR_ARG, bad == kdbplan::LAYOUT_ENTRIES ? "kdb_record_tables: more than 2^31 table entries (records x 4^k) in one call"
-                                 : bad == kdbplan::LAYOUT_ENDS  ? "read_offsets must start at 0 and end at nbytes"
-                                                                : "read_offsets must rise from 0 to nbytes");
+        return bad != kdbplan::LAYOUT_ENTRIES ? record_offsets_fail(bad)
+                                              : fail(KDB_ERR_ARG, "kdb_record_tables: more than 2^31 table entries (records x 4^k) in one call");
     // so are the residues: every byte is one of ACGTN, or nothing is launched
     if (const uint64_t nbad = residues_outside_acgtn(bases, nbytes)) return fail(KDB_ERR_BAD_RESIDUE, "kdb_record_tables: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
     const uint64_t npieces = lay.npieces, nbins = 1ull << (2 * k), nmulti = lay.multi.size();
     AnalysisCall call;
     if (int rc = call.open(device_id)) return rc;
 
-    auto *d_bases = call.alloc<uint8_t>(((nbytes + 15) & ~(size_t)15) + 32);           // (tables_piece_kernel's aligned words reach 15 bytes past a window's start)
-    auto *d_offs = call.alloc<uint64_t>(nreads + 1);
-    auto *rec_piece0 = call.alloc<uint32_t>(nreads + 1), *piece_rec = nmulti ? call.alloc<uint32_t>(npieces) : nullptr;
+    RecordBatch in;
+    const bool staged = in.alloc(call, nbytes, nreads, lay, 32);                       // (tables_piece_kernel's aligned words reach 15 bytes past a window's start)
     auto *multi = nmulti ? call.alloc<uint32_t>(nmulti) : nullptr;
     auto *pieces = call.alloc<kdbtables::PieceOut>(npieces);
     auto *tables = call.alloc<uint32_t>(nreads * nbins);
     auto *counts = call.alloc<unsigned long long>(2 * nreads);
     auto *ends = call.alloc<int32_t>(2 * nreads);
-    if (!d_bases || !d_offs || !rec_piece0 || (nmulti && (!piece_rec || !multi)) || !pieces || !tables || !counts || !ends)
+    if (!staged || (nmulti && !multi) || !pieces || !tables || !counts || !ends)
         return fail(KDB_ERR_NOMEM, "kdb_record_tables: no room for the scratch of %zu residues in %zu records of 4^%d entries", nbytes, nreads, k);
-    if (nbytes) HIP_TRY(hipMemcpyAsync(d_bases, bases, nbytes, hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(rec_piece0, lay.rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    if (nmulti) {
-        HIP_TRY(hipMemcpyAsync(piece_rec, lay.piece_rec.data(), npieces * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-        HIP_TRY(hipMemcpyAsync(multi, lay.multi.data(), nmulti * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    }
+    if (int rc = in.upload(call, bases, nbytes, offs, nreads, lay)) return rc;
+    if (nmulti) HIP_TRY(hipMemcpyAsync(multi, lay.multi.data(), nmulti * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
     HIP_TRY(call.begin());
     if (nmulti)
         hipLaunchKernelGGL(kdbtables::tables_zero_kernel, dim3((unsigned)std::min<uint64_t>(nmulti, 4096)), dim3(256), 0, call.st, (const uint32_t *)multi,
                            (uint32_t)nmulti, k, tables);
     hipLaunchKernelGGL(kdbtables::tables_piece_kernel, dim3((unsigned)((npieces + kdbtables::WAVES - 1) / kdbtables::WAVES)), dim3(kdbtables::TPB),
-                       kdbtables::lds_bytes(k), call.st, (const uint8_t *)d_bases, (const uint64_t *)d_offs, (const uint32_t *)piece_rec,
-                       (const uint32_t *)rec_piece0, (uint32_t)npieces, k, stride, canonical ? 1 : 0, (uint32_t)phase, tables, pieces);
+                       kdbtables::lds_bytes(k), call.st, (const uint8_t *)in.bases, (const uint64_t *)in.offs, (const uint32_t *)in.piece_rec,
+                       (const uint32_t *)in.rec_piece0, (uint32_t)npieces, k, stride, canonical ? 1 : 0, (uint32_t)phase, tables, pieces);
     hipLaunchKernelGGL(kdbtables::tables_record_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, call.st, (const kdbtables::PieceOut *)pieces,
-                       (const uint32_t *)rec_piece0, (uint64_t)nreads, counts, counts + nreads, ends, ends + nreads);
+                       (const uint32_t *)in.rec_piece0, (uint64_t)nreads, counts, counts + nreads, ends, ends + nreads);
     HIP_TRY(hipGetLastError());
     HIP_TRY(call.end());
     HIP_TRY(hipMemcpyAsync(tables_out, tables, nreads * nbins * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
@@ -714,50 +751,42 @@ int kdb_minimizers(int device_id, int k, int w, int canonical, int order, const 
     if (w < 1 || w > km::MAX_W) return fail(KDB_ERR_ARG, "kdb_minimizers: w=%d out of range 1..%d", w, km::MAX_W);
     if (order != KDB_MINIMIZER_LEX && order != KDB_MINIMIZER_HASHED) return fail(KDB_ERR_ARG, "kdb_minimizers: unknown order %d", order);
     if (!total_out) return fail(KDB_ERR_ARG, "kdb_minimizers: total_out must not be NULL");
+    if (int rc = record_check_args("kdb_minimizers", bases, nbytes, offs, nreads, counts_out != nullptr)) return rc;
     if (nreads == 0) {
-        if (nbytes != 0) return fail(KDB_ERR_ARG, "kdb_minimizers: residues but no records");
         *total_out = 0;
         return KDB_OK;
     }
-    if (!offs || (!bases && nbytes) || !counts_out) return fail(KDB_ERR_ARG, "kdb_minimizers: NULL buffer");
     if (cap > 0 && (!ids_out || !pos_out)) return fail(KDB_ERR_ARG, "kdb_minimizers: ids_out and pos_out must not be NULL where cap > 0");
-    if (nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_minimizers: at most 2^30 residues per call");
-    if (nreads > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_minimizers: at most 2^30 records per call");
+    if (int rc = record_check_sizes("kdb_minimizers", nbytes, nreads)) return rc;
     // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
     kdbplan::MinimizersLayout lay;
-    if (const kdbplan::LayoutError bad = kdbplan::minimizers_layout(offs, nreads, nbytes, k, (uint32_t)w, km::PIECE, lay))
-        return fail(KDB_ERR_ARG, bad == kdbplan::LAYOUT_ENDS ? "read_offsets must start at 0 and end at nbytes" : "read_offsets must rise from 0 to nbytes");
+    if (const kdbplan::LayoutError bad = kdbplan::minimizers_layout(offs, nreads, nbytes, k, (uint32_t)w, km::PIECE, lay)) return record_offsets_fail(bad);
     // so are the residues: every byte is one of ACGTN, or nothing is launched
     if (const uint64_t nbad = residues_outside_acgtn(bases, nbytes)) return fail(KDB_ERR_BAD_RESIDUE, "kdb_minimizers: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
     const uint32_t npieces = (uint32_t)lay.npieces, nblocks = (npieces + km::SCAN_BLOCK - 1) / km::SCAN_BLOCK;
-    const bool multi = !lay.piece_rec.empty();
     AnalysisCall call;
     if (int rc = call.open(device_id)) return rc;
 
     // (select_kernel's aligned words reach 3 bytes past a record's end, emit_kernel's five 39 bytes past a window's start)
-    auto *d_bases = call.alloc<uint8_t>(((nbytes + 15) & ~(size_t)15) + 64);
-    auto *d_offs = call.alloc<uint64_t>(nreads + 1);
-    auto *rec_piece0 = call.alloc<uint32_t>(nreads + 1), *piece_rec = multi ? call.alloc<uint32_t>(npieces) : nullptr;
+    RecordBatch in;
+    const bool staged = in.alloc(call, nbytes, nreads, lay, 64);
     auto *flags = call.alloc<uint8_t>(nbytes + 16);
     auto *piece_count = call.alloc<uint32_t>(npieces), *piece_off = call.alloc<uint32_t>((uint64_t)npieces + 1), *sums = call.alloc<uint32_t>(nblocks);
     auto *counts = call.alloc<unsigned long long>(nreads);
-    if (!d_bases || !d_offs || !rec_piece0 || (multi && !piece_rec) || !flags || !piece_count || !piece_off || !sums || !counts)
+    if (!staged || !flags || !piece_count || !piece_off || !sums || !counts)
         return fail(KDB_ERR_NOMEM, "kdb_minimizers: no room for the scratch of %zu residues in %zu records", nbytes, nreads);
-    if (nbytes) HIP_TRY(hipMemcpyAsync(d_bases, bases, nbytes, hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_offs, offs, (nreads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(rec_piece0, lay.rec_piece0.data(), (nreads + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    if (multi) HIP_TRY(hipMemcpyAsync(piece_rec, lay.piece_rec.data(), (size_t)npieces * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+    if (int rc = in.upload(call, bases, nbytes, offs, nreads, lay)) return rc;
     const dim3 piece_grid((npieces + km::WAVES - 1) / km::WAVES);
     uint32_t total = 0;
     HIP_TRY(call.begin());
-    hipLaunchKernelGGL(km::select_kernel, piece_grid, dim3(km::TPB), (size_t)km::WAVES * lay.lds_wave, call.st, (const uint8_t *)d_bases, (const uint64_t *)d_offs,
-                       (const uint32_t *)piece_rec, (const uint32_t *)rec_piece0, npieces, k, (uint32_t)w, canonical ? 1 : 0, order, lay.max_keys, lay.lds_wave, flags,
+    hipLaunchKernelGGL(km::select_kernel, piece_grid, dim3(km::TPB), (size_t)km::WAVES * lay.lds_wave, call.st, (const uint8_t *)in.bases, (const uint64_t *)in.offs,
+                       (const uint32_t *)in.piece_rec, (const uint32_t *)in.rec_piece0, npieces, k, (uint32_t)w, canonical ? 1 : 0, order, lay.max_keys, lay.lds_wave, flags,
                        piece_count);
     hipLaunchKernelGGL(km::scan_sums_kernel, dim3(nblocks), dim3(km::SCAN_TPB), 0, call.st, (const uint32_t *)piece_count, npieces, sums);
     hipLaunchKernelGGL(km::scan_top_kernel, dim3(1), dim3(km::SCAN_TPB), 0, call.st, sums, nblocks, piece_off + npieces);
     hipLaunchKernelGGL(km::scan_apply_kernel, dim3(nblocks), dim3(km::SCAN_TPB), 0, call.st, (const uint32_t *)piece_count, npieces, (const uint32_t *)sums, piece_off);
     hipLaunchKernelGGL(km::record_counts_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, call.st, (const uint32_t *)piece_off,
-                       (const uint32_t *)rec_piece0, (uint64_t)nreads, counts);
+                       (const uint32_t *)in.rec_piece0, (uint64_t)nreads, counts);
     HIP_TRY(hipGetLastError());
     HIP_TRY(call.end());
     HIP_TRY(hipMemcpyAsync(&total, piece_off + npieces, sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
@@ -774,8 +803,8 @@ int kdb_minimizers(int device_id, int k, int w, int canonical, int order, const 
         d_strand = strand_out ? call.alloc<uint8_t>(total) : nullptr;
         if (!d_ids || !d_pos || (strand_out && !d_strand)) return fail(KDB_ERR_NOMEM, "kdb_minimizers: no room for the lists of %u minimizers", total);
         HIP_TRY(call.begin());
-        hipLaunchKernelGGL(km::emit_kernel, piece_grid, dim3(km::TPB), 0, call.st, (const uint8_t *)d_bases, (const uint64_t *)d_offs, (const uint32_t *)piece_rec,
-                           (const uint32_t *)rec_piece0, npieces, k, canonical ? 1 : 0, (const uint8_t *)flags, (const uint32_t *)piece_off, (unsigned long long *)d_ids,
+        hipLaunchKernelGGL(km::emit_kernel, piece_grid, dim3(km::TPB), 0, call.st, (const uint8_t *)in.bases, (const uint64_t *)in.offs, (const uint32_t *)in.piece_rec,
+                           (const uint32_t *)in.rec_piece0, npieces, k, canonical ? 1 : 0, (const uint8_t *)flags, (const uint32_t *)piece_off, (unsigned long long *)d_ids,
                            d_pos, d_strand);
         HIP_TRY(hipGetLastError());
         HIP_TRY(call.end());

@@ -1,8 +1,10 @@
 // kdb_sweep_plan.cpp.h -- the host-only plans of the analysis calls (plain C++, no HIP: tests/c/sweep_plan_check.cpp compiles it alone, runs
 // it under the sanitizers and prints the plans for tests/sweep_cases.py to be compared with): which block pairs become which launch rows,
-// in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, and how the records of
-// kdb_score_reads, of kdb_record_tables (tests/c/tables_plan_check.cpp) and of kdb_minimizers (tests/c/minimizers_plan_check.cpp) split into pieces,
-// and the window, the stages and the LDS of a task of kdb_align_banded (tests/c/alignment_plan_check.cpp).  The block size, HALF, the chunk sizes, the piece size and the stage are arguments: the kernel headers have them.
+// in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, the one check of record
+// offsets (check_offsets) and the one split of records into pieces (RecordLayout, record_layout) that kdb_score_reads, kdb_record_tables
+// (tests/c/tables_plan_check.cpp) and kdb_minimizers (tests/c/minimizers_plan_check.cpp) share -- each adds how many windows a record has and
+// what else it asks of its records --, and the window, the stages and the LDS of a task of kdb_align_banded (tests/c/alignment_plan_check.cpp).
+// The block size, HALF, the chunk sizes, the piece size and the stage are arguments: the kernel headers have them.
 // A row type is the kernel header's (kdbgram::Row, kdbpair::Row, kdbpair::FloatRow) or any struct of as many uint8_t fields.
 #pragma once
 #include <cstdint>
@@ -91,39 +93,72 @@ inline Grid sweep_grid(uint64_t nbins, uint32_t chunk_bins, uint32_t wg_chunks, 
 // the most workgroups per row of a sweep with nrows rows: from many_rows rows on the rows fill the device and the smaller cap does
 inline uint32_t rows_cap(uint32_t nrows, uint32_t many_rows, uint32_t cap, uint32_t cap_many_rows) { return nrows < many_rows ? cap : cap_many_rows; }
 
-// kdb_score_reads: record r is pieces rec_piece0[r] .. rec_piece0[r + 1], of at most `piece` windows each and at least one (a record
-// without a window has an empty one); piece_rec[p] = the record of piece p, left empty when every record is one piece.  offs: nreads + 1
-// offsets into nbytes residues, nreads >= 1.  A record shorter than k counts as short unless it is the first and `continues` an earlier
-// call's; where there are short records piece_rec is left empty too: the caller refuses them.
+// The per-record calls (kdb_score_reads, kdb_record_tables, kdb_minimizers) take nbytes residues and the nreads + 1 offsets of their records,
+// nreads >= 1, and share one layout; kdb_align_banded takes two such buffers.
 enum LayoutError { LAYOUT_OK = 0, LAYOUT_ENDS /* must start at 0 and end at nbytes */, LAYOUT_RISE /* must rise from 0 to nbytes */,
                    LAYOUT_ENTRIES /* kdb_record_tables: more table entries than the call allows */,
                    LAYOUT_TASK, LAYOUT_STRAND, LAYOUT_QUERY /* kdb_align_banded: a task's record index, its strand, its query's length */ };
 
-struct ScoreLayout {
+// offs: n + 1 offsets into nbytes residues; where both fail it is LAYOUT_ENDS.  each(r, len) is given the records in order, in the same
+// pass, as far as their offsets rise.
+template <class Each>
+LayoutError check_offsets(const uint64_t *offs, size_t n, uint64_t nbytes, Each each)
+{
+    if (offs[0] != 0 || offs[n] != nbytes) return LAYOUT_ENDS;
+    for (size_t r = 0; r < n; r++) {
+        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
+        each(r, offs[r + 1] - offs[r]);
+    }
+    return LAYOUT_OK;
+}
+
+inline LayoutError check_offsets(const uint64_t *offs, size_t n, uint64_t nbytes) { return check_offsets(offs, n, nbytes, [](size_t, uint64_t) {}); }
+
+// Record r is pieces rec_piece0[r] .. rec_piece0[r + 1], of at most `piece` windows each and at least one (a record without a window has
+// an empty one); piece_rec[p] = the record of piece p, left empty when every record is one piece.  A refused layout is an empty one.
+struct RecordLayout {
     std::vector<uint32_t> rec_piece0, piece_rec;
-    uint64_t npieces = 0, nshort = 0;
+    uint64_t npieces = 0;
 };
 
-inline LayoutError score_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, int k, uint32_t piece, bool continues, ScoreLayout &lay)
+// The layout (a RecordLayout, or a call's own with more members) of the records that check_offsets() passes.  windows(r, len): how many
+// windows record r, of len residues, has -- all a call has of its own here.  It is asked once per record, in order, so it may note in
+// `lay` what else the call wants to know of its records.
+template <class Layout, class Windows>
+LayoutError record_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, uint32_t piece, Windows windows, Layout &lay)
 {
-    lay = ScoreLayout();
-    if (offs[0] != 0 || offs[nreads] != nbytes) return LAYOUT_ENDS;
+    lay = Layout();
     lay.rec_piece0.resize(nreads + 1);
-    for (size_t r = 0; r < nreads; r++) {
-        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
-        const uint64_t len = offs[r + 1] - offs[r];
-        if (len < (uint64_t)k && !(r == 0 && continues)) lay.nshort++;
-        const uint64_t nwin = len >= (uint64_t)k ? len - (uint64_t)k + 1 : 0;
+    const LayoutError bad = check_offsets(offs, nreads, nbytes, [&](size_t r, uint64_t len) {
         lay.rec_piece0[r] = (uint32_t)lay.npieces;
-        lay.npieces += std::max<uint64_t>(1, (nwin + piece - 1) / piece);         // (< 2^31: 2^30 records and 2^30 windows at most)
+        lay.npieces += std::max<uint64_t>(1, (windows(r, len) + piece - 1) / piece);                       // (< 2^31: 2^30 records and 2^30 windows at most)
+    });
+    if (bad) {
+        lay = Layout();
+        return bad;
     }
     lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
-    if (lay.nshort == 0 && lay.npieces != nreads) {
+    if (lay.npieces != nreads) {
         lay.piece_rec.resize(lay.npieces);
         for (size_t r = 0; r < nreads; r++)
             for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
     }
     return LAYOUT_OK;
+}
+
+// kdb_score_reads: a record of len residues has the windows 0 .. len - k.  One shorter than k counts as short unless it is the first and
+// `continues` an earlier call's; where there are short records piece_rec is left empty: the caller refuses them.
+struct ScoreLayout : RecordLayout { uint64_t nshort = 0; };
+
+inline LayoutError score_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, int k, uint32_t piece, bool continues, ScoreLayout &lay)
+{
+    auto windows = [&](size_t r, uint64_t len) {
+        if (len < (uint64_t)k && !(r == 0 && continues)) lay.nshort++;
+        return len >= (uint64_t)k ? len - (uint64_t)k + 1 : 0;
+    };
+    const LayoutError bad = record_layout(offs, nreads, nbytes, piece, windows, lay);
+    if (lay.nshort) lay.piece_rec.clear();
+    return bad;
 }
 
 // kdb_record_tables: the windows of a record of len residues start at phase + i stride, for every i with phase + i stride + k <= len
@@ -133,14 +168,11 @@ constexpr uint64_t tables_windows(uint64_t len, int k, int stride, uint64_t phas
     return len >= (uint64_t)k + phase ? (len - (uint64_t)k - phase) / (uint64_t)stride + 1 : 0;
 }
 
-// Record r is pieces rec_piece0[r] .. rec_piece0[r + 1] of at most `piece` windows each and at least one (a record without a window has an
-// empty one): piece p of it holds the windows (p - rec_piece0[r]) piece .. of the record's tables_windows(), `phase` for record 0 and 0 for
-// the others.  piece_rec[p] = the record of piece p, left empty when every record is one piece.  multi: the records of more than one
-// piece, in order -- their rows are added to by several waves and are zeroed first; every other row is stored whole by its only wave.
-// LAYOUT_ENTRIES: nreads 4^k is above max_entries.
-struct TablesLayout {
-    std::vector<uint32_t> rec_piece0, piece_rec, multi;
-    uint64_t npieces = 0;
+// Piece p of record r holds the windows (p - rec_piece0[r]) piece .. of the record's tables_windows(), `phase` for record 0 and 0 for the
+// others.  multi: the records of more than one piece, in order -- their rows are added to by several waves and are zeroed first; every
+// other row is stored whole by its only wave.  LAYOUT_ENTRIES: nreads 4^k is above max_entries.
+struct TablesLayout : RecordLayout {
+    std::vector<uint32_t> multi;
     // the windows [first, first + count) of piece p of record r, which has nwin of them
     static void piece_windows(uint64_t nwin, uint32_t p_in_rec, uint32_t piece, uint64_t &first, uint32_t &count)
     {
@@ -153,25 +185,16 @@ inline LayoutError tables_layout(const uint64_t *offs, size_t nreads, uint64_t n
                                  TablesLayout &lay)
 {
     lay = TablesLayout();
-    if (offs[0] != 0 || offs[nreads] != nbytes) return LAYOUT_ENDS;
-    for (size_t r = 0; r < nreads; r++)
-        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
-    if ((uint64_t)nreads > (max_entries >> (2 * k))) return LAYOUT_ENTRIES;
-    lay.rec_piece0.resize(nreads + 1);
-    for (size_t r = 0; r < nreads; r++) {
-        const uint64_t nwin = tables_windows(offs[r + 1] - offs[r], k, stride, r == 0 ? phase : 0);
-        const uint64_t n = std::max<uint64_t>(1, (nwin + piece - 1) / piece);
-        lay.rec_piece0[r] = (uint32_t)lay.npieces;
-        lay.npieces += n;                                                         // (< 2^31: 2^30 records and 2^30 windows at most)
-        if (n > 1) lay.multi.push_back((uint32_t)r);
+    if ((uint64_t)nreads > (max_entries >> (2 * k))) {                            // refused, but what its offsets are refused for comes first
+        const LayoutError bad = check_offsets(offs, nreads, nbytes);
+        return bad ? bad : LAYOUT_ENTRIES;
     }
-    lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
-    if (!lay.multi.empty()) {
-        lay.piece_rec.resize(lay.npieces);
-        for (size_t r = 0; r < nreads; r++)
-            for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
-    }
-    return LAYOUT_OK;
+    auto windows = [&](size_t r, uint64_t len) {
+        const uint64_t nwin = tables_windows(len, k, stride, r == 0 ? phase : 0);
+        if (nwin > piece) lay.multi.push_back((uint32_t)r);
+        return nwin;
+    };
+    return record_layout(offs, nreads, nbytes, piece, windows, lay);
 }
 
 // kdb_minimizers: a record of len residues has the start positions 0 .. len - k (constexpr: the kernels count them with the same expression)
@@ -193,43 +216,24 @@ constexpr MinimizerPiece minimizer_piece(uint64_t nwin, uint32_t p_in_rec, uint3
     return MinimizerPiece{first, lo, hi, count};
 }
 
-// Record r is pieces rec_piece0[r] .. rec_piece0[r + 1], of at most `piece` start positions each and at least one (a record without a
-// start position has an empty one); piece_rec[p] = the record of piece p, left empty when every record is one piece.  max_keys: the most
-// keys any piece reads; lds_wave: the bytes of LDS a wave then needs, a multiple of 8 -- max_keys keys of 8 bytes, then the residues
-// behind them, read as aligned 4-byte words (up to 3 bytes before the first and after the last).
-struct MinimizersLayout {
-    std::vector<uint32_t> rec_piece0, piece_rec;
-    uint64_t npieces = 0;
-    uint32_t max_keys = 0, lds_wave = 0;
-};
+// The windows of the layout are the start positions.  max_keys: the most keys any piece reads; lds_wave: the bytes of LDS a wave then
+// needs, a multiple of 8 -- max_keys keys of 8 bytes, then the residues behind them, read as aligned 4-byte words (up to 3 bytes before
+// the first and after the last).
+struct MinimizersLayout : RecordLayout { uint32_t max_keys = 0, lds_wave = 0; };
 
 inline LayoutError minimizers_layout(const uint64_t *offs, size_t nreads, uint64_t nbytes, int k, uint32_t w, uint32_t piece, MinimizersLayout &lay)
 {
-    lay = MinimizersLayout();
-    if (offs[0] != 0 || offs[nreads] != nbytes) return LAYOUT_ENDS;
-    for (size_t r = 0; r < nreads; r++)
-        if (offs[r + 1] < offs[r] || offs[r + 1] > nbytes) return LAYOUT_RISE;
-    lay.rec_piece0.resize(nreads + 1);
-    bool multi = false;
-    for (size_t r = 0; r < nreads; r++) {
-        const uint64_t nwin = minimizer_positions(offs[r + 1] - offs[r], k);
-        const uint64_t n = std::max<uint64_t>(1, (nwin + piece - 1) / piece);
-        lay.rec_piece0[r] = (uint32_t)lay.npieces;
-        lay.npieces += n;                                                         // (< 2^31: 2^30 records and 2^30 positions at most)
-        multi = multi || n > 1;
-        for (uint64_t p = 0; p < n; p++) {
+    auto windows = [&](size_t, uint64_t len) {
+        const uint64_t nwin = minimizer_positions(len, k);
+        for (uint64_t p = 0; p * piece < nwin; p++) {
             const MinimizerPiece pc = minimizer_piece(nwin, (uint32_t)p, piece, w);
             lay.max_keys = std::max(lay.max_keys, (uint32_t)(pc.hi - pc.lo));
         }
-    }
-    lay.rec_piece0[nreads] = (uint32_t)lay.npieces;
-    lay.lds_wave = lay.max_keys * 8u + ((lay.max_keys + (uint32_t)k + 6u + 7u) & ~7u);
-    if (multi) {
-        lay.piece_rec.resize(lay.npieces);
-        for (size_t r = 0; r < nreads; r++)
-            for (uint32_t p = lay.rec_piece0[r]; p < lay.rec_piece0[r + 1]; p++) lay.piece_rec[p] = (uint32_t)r;
-    }
-    return LAYOUT_OK;
+        return nwin;
+    };
+    const LayoutError bad = record_layout(offs, nreads, nbytes, piece, windows, lay);
+    if (!bad) lay.lds_wave = lay.max_keys * 8u + ((lay.max_keys + (uint32_t)k + 6u + 7u) & ~7u);
+    return bad;
 }
 
 // kdb_align_banded: a task aligns an oriented query of m residues to a reference record of n around the diagonal d, j - i = d, inside
@@ -287,11 +291,8 @@ inline LayoutError align_layout(const uint64_t *q_offs, size_t nq, uint64_t q_nb
                                 uint32_t waves, uint32_t grid_max, AlignLayout &lay)
 {
     lay = AlignLayout();
-    if (q_offs[0] != 0 || q_offs[nq] != q_nbytes || r_offs[0] != 0 || r_offs[nr] != r_nbytes) return LAYOUT_ENDS;
-    for (size_t r = 0; r < nq; r++)
-        if (q_offs[r + 1] < q_offs[r] || q_offs[r + 1] > q_nbytes) return LAYOUT_RISE;
-    for (size_t r = 0; r < nr; r++)
-        if (r_offs[r + 1] < r_offs[r] || r_offs[r + 1] > r_nbytes) return LAYOUT_RISE;
+    const LayoutError bad_q = check_offsets(q_offs, nq, q_nbytes), bad_r = check_offsets(r_offs, nr, r_nbytes);
+    if (bad_q || bad_r) return bad_q == LAYOUT_ENDS || bad_r == LAYOUT_ENDS ? LAYOUT_ENDS : LAYOUT_RISE;      // (the ends of both buffers come first)
     uint64_t cells = 0, nonempty = 0;
     for (size_t t = 0; t < ntasks; t++) {
         lay.bad = t;

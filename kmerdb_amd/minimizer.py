@@ -13,12 +13,11 @@ import sys
 
 import numpy as np
 
-from . import _abi
+from . import _abi, _records
 
 MAX_K, MAX_W = _abi.KDB_MINIMIZER_MAX_K, _abi.KDB_MINIMIZER_MAX_W
 ORDERS = {"lexicographic": _abi.KDB_MINIMIZER_LEX, "hashed": _abi.KDB_MINIMIZER_HASHED}
 SMALL_BATCH = 1 << 22                      # residues up to which the lists are sized for a minimizer at every position: no second call
-_MAX_RESIDUES = 1 << 30                    # per kdb_minimizers call
 
 
 def _check_scalars(k, w, order):
@@ -35,21 +34,6 @@ def _check_scalars(k, w, order):
     if order not in ORDERS:
         raise ValueError("kmerdb_amd.minimizer: order={0!r} is neither 'lexicographic' nor 'hashed'".format(order))
     return k, w, ORDERS[order]
-
-
-def _check_batch(bases, offsets):
-    if isinstance(bases, (bytes, bytearray, memoryview)):
-        bases = np.frombuffer(bases, dtype=np.uint8)
-    if not isinstance(bases, np.ndarray) or bases.dtype != np.uint8 or bases.ndim != 1:
-        raise TypeError("kmerdb_amd.minimizer: bases must be bytes or a one-dimensional uint8 array")
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    if offsets.ndim != 1 or offsets.size < 1:
-        raise ValueError("kmerdb_amd.minimizer: offsets must hold nreads + 1 entries")
-    if int(offsets[0]) != 0 or int(offsets[-1]) != bases.size or np.any(offsets[1:] < offsets[:-1]):
-        raise ValueError("read_offsets must rise from 0 to nbytes")
-    if bases.size > _MAX_RESIDUES:
-        raise ValueError("kmerdb_amd.minimizer: at most 2^30 residues per call")
-    return np.ascontiguousarray(bases), offsets
 
 
 def minimizers_raw(bases, offsets, k, w, canonical, order, cap, device=0):
@@ -85,7 +69,7 @@ def minimizers(bases, offsets, k, w, canonical=True, order="lexicographic", devi
     k-mer id (canonical: the smaller of both strands'), the start position inside the record, and 1 where the id is the reverse
     strand's.  ValueError for what the call refuses: a residue outside upper-case ACGTN."""
     k, w, order = _check_scalars(k, w, order)
-    bases, offsets = _check_batch(bases, offsets)
+    bases, offsets = _records.check_batch("minimizer", bases, offsets)
     from .distance import _require_device
     _require_device(device)
     counts, ids, pos, strand, total, _ = minimizers_raw(bases, offsets, k, w, canonical, order, list_capacity(int(bases.size), w), device)

@@ -12,11 +12,10 @@ import sys
 
 import numpy as np
 
-from . import _abi, fileutil
+from . import _abi, _records, fileutil
 
 COLUMNS = ("id", "length", "windows", "zero_windows", "min_count", "log10_p", "log_odds_ratio")
 NO_COUNT = 2 ** 64 - 1                     # min_count of a record without a scored window
-_MAX_RESIDUES = 1 << 30                    # per kdb_score_reads call
 
 
 def log_odds_ratio(log10_p, k):
@@ -43,21 +42,6 @@ def _check_scalars(k, total, pseudocount):
     if total + pseudocount * 4 ** k >= 2 ** 64 or 4 * pseudocount >= 2 ** 64:
         raise ValueError("kmerdb_amd.probability: total + pseudocount * 4^k and 4 * pseudocount must stay below 2^64")
     return k, total, pseudocount
-
-
-def _check_batch(bases, offsets):
-    if isinstance(bases, (bytes, bytearray, memoryview)):
-        bases = np.frombuffer(bases, dtype=np.uint8)
-    if not isinstance(bases, np.ndarray) or bases.dtype != np.uint8 or bases.ndim != 1:
-        raise TypeError("kmerdb_amd.probability: bases must be bytes or a one-dimensional uint8 array")
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    if offsets.ndim != 1 or offsets.size < 1:
-        raise ValueError("kmerdb_amd.probability: offsets must hold nreads + 1 entries")
-    if int(offsets[0]) != 0 or int(offsets[-1]) != bases.size or np.any(offsets[1:] < offsets[:-1]):
-        raise ValueError("read_offsets must rise from 0 to nbytes")
-    if bases.size > _MAX_RESIDUES:
-        raise ValueError("kmerdb_amd.probability: at most 2^30 residues per call")
-    return np.ascontiguousarray(bases), offsets
 
 
 def _vector_pointer(vector, k, device):
@@ -100,7 +84,7 @@ def score_reads(bases, offsets, vector, k, canonical, total, pseudocount=0, cont
     piece of the previous call's last record (KDB_SCORE_CONTINUES).  ValueError for what the engine refuses (a record shorter than k, a
     residue outside ACGTN); log10_p is -inf for a record with a k-mer the profile lacks (pseudocount 0), nan for one without a scored window."""
     k, total, pseudocount = _check_scalars(k, total, pseudocount)
-    bases, offsets = _check_batch(bases, offsets)
+    bases, offsets = _records.check_batch("probability", bases, offsets)
     pointer, keep = _vector_pointer(vector, k, device)
     from .distance import _require_device
     _require_device(device)

@@ -32,6 +32,7 @@ static void do_minimizers(int k, uint32_t w, uint32_t piece, uint64_t nbytes, co
     const size_t nreads = offs.size() - 1;
     kdbplan::MinimizersLayout lay;
     const kdbplan::LayoutError e = kdbplan::minimizers_layout(offs.data(), nreads, nbytes, k, w, piece, lay);
+    CHECK(e == kdbplan::check_offsets(offs.data(), nreads, nbytes));
     if (e != kdbplan::LAYOUT_OK) {
         printf("refused %s\n", e == kdbplan::LAYOUT_ENDS ? "ends" : "rise");
         CHECK(lay.rec_piece0.empty() && lay.piece_rec.empty() && lay.npieces == 0 && lay.max_keys == 0 && lay.lds_wave == 0);

@@ -127,8 +127,13 @@ static void do_score(int k, uint32_t piece, bool continues, uint64_t nbytes, con
     const size_t nreads = offs.size() - 1;
     kdbplan::ScoreLayout lay;
     const kdbplan::LayoutError e = kdbplan::score_layout(offs.data(), nreads, nbytes, k, piece, continues, lay);
+    CHECK(e == kdbplan::check_offsets(offs.data(), nreads, nbytes));
     printf("score k=%d continues=%d nbytes=%llu offs=%s:", k, (int)continues, (unsigned long long)nbytes, csv);
-    if (e != kdbplan::LAYOUT_OK) { printf(" error=%s\n", e == kdbplan::LAYOUT_ENDS ? "ends" : "rise"); return; }
+    if (e != kdbplan::LAYOUT_OK) {
+        printf(" error=%s\n", e == kdbplan::LAYOUT_ENDS ? "ends" : "rise");
+        CHECK(lay.rec_piece0.empty() && lay.piece_rec.empty() && lay.npieces == 0 && lay.nshort == 0);
+        return;
+    }
     CHECK(lay.rec_piece0.size() == nreads + 1 && lay.rec_piece0[0] == 0 && lay.rec_piece0[nreads] == lay.npieces && lay.npieces >= nreads);
     CHECK(lay.piece_rec.empty() || lay.piece_rec.size() == lay.npieces);
     for (size_t p = 0; p < lay.piece_rec.size(); p++)

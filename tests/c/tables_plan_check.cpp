@@ -32,6 +32,8 @@ static void do_tables(int k, int stride, uint64_t phase, uint32_t piece, uint64_
     const size_t nreads = offs.size() - 1;
     kdbplan::TablesLayout lay;
     const kdbplan::LayoutError e = kdbplan::tables_layout(offs.data(), nreads, nbytes, k, stride, phase, piece, max_entries, lay);
+    // the offsets are judged first, the entries after them
+    CHECK(kdbplan::check_offsets(offs.data(), nreads, nbytes) == (e == kdbplan::LAYOUT_ENTRIES ? kdbplan::LAYOUT_OK : e));
     if (e != kdbplan::LAYOUT_OK) {
         printf("refused %s\n", e == kdbplan::LAYOUT_ENDS ? "ends" : e == kdbplan::LAYOUT_RISE ? "rise" : "entries");
         CHECK(lay.rec_piece0.empty() && lay.piece_rec.empty() && lay.multi.empty() && lay.npieces == 0);

@@ -189,6 +189,13 @@ def ladder_lengths(k, w, piece):
     return small + [length_for(n, k) for n in wins]
 
 
+def layout_edges(k, piece):
+    """the batches at the edges of kdb_minimizers' piece layout -> (record lengths, start positions of every record)"""
+    one, two = length_for(piece, k), length_for(piece + 1, k)
+    return [([0], [0]), ([k - 1], [0]), ([one], [piece]), ([two], [piece + 1]), ([one, two], [piece, piece + 1]), ([two, one], [piece + 1, piece]),
+            ([k, k, one, two], [1, 1, piece, piece + 1])]                                                  # only the last record is cut
+
+
 def ladder_records(k, w, piece, seed, p_n=0.001):
     """records at every edge of the kernel, single-piece and multi-piece ones interleaved"""
     rng = np.random.Generator(np.random.PCG64(seed))

@@ -194,6 +194,15 @@ def length_ladder(k, piece):
     return [w + k - 1 for w in (1, 2, 63, 64, 65, piece - 1, piece, piece + 1, 2 * piece + 1)]
 
 
+def layout_edges(k, piece):
+    """the batches at the edges of kdb_score_reads' piece layout -> (record lengths, continues, short records, pieces of every record)"""
+    one, two = piece + k - 1, piece + k                # `piece` windows, and one more
+    return [([0], False, 1, [1]), ([0], True, 0, [1]),
+            ([k - 1], False, 1, [1]), ([k - 1], True, 0, [1]), ([k - 1, k - 1], True, 1, [1, 1]),          # (only record 0 may continue)
+            ([one], False, 0, [1]), ([two], False, 0, [2]), ([one, two], False, 0, [1, 2]), ([two, one], False, 0, [2, 1]),
+            ([k, k, one, two], False, 0, [1, 1, 1, 2])]                                                # only the last record is cut
+
+
 def ladder_records(k, piece, seed, p_n=0.0):
     rng = np.random.default_rng(seed)
     return [random_record(rng, n, p_n) for n in length_ladder(k, piece)]

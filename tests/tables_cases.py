@@ -111,6 +111,16 @@ def length_for(nwin, k, stride):
     return 0 if nwin == 0 else (nwin - 1) * stride + k
 
 
+def layout_edges(k, stride, piece):
+    """the batches at the edges of kdb_record_tables' piece layout -> (record lengths, phase of record 0, windows of every record)"""
+    one, two, ph = length_for(piece, k, stride), length_for(piece + 1, k, stride), stride - 1
+    return [([0], 0, [0]), ([k - 1], 0, [0]), ([k - 1 + ph], ph, [0]), ([k + ph], ph, [1]),
+            ([one], 0, [piece]), ([two], 0, [piece + 1]), ([one, two], 0, [piece, piece + 1]), ([two, one], 0, [piece + 1, piece]),
+            ([k, k, one, two], 0, [1, 1, piece, piece + 1]),                                               # only the last record is cut
+            ([one + ph, one], ph, [piece, piece]), ([two + ph, one], ph, [piece + 1, piece]),              # the phase is record 0's alone
+            ([two, two], ph, [piece + (0 if ph else 1), piece + 1])]                                       # ... and can take its last window away
+
+
 def ladder_records(k, stride, piece, seed, p_n=0.002):
     """Records at every edge of the kernel: 0, 1, k - 1, k, k + 1 residues, and 63, 64, 65, piece - 1, piece, piece + 1, 2 piece + 1
     windows (the last window's residues, then stride - 1 more that open no window), single-piece and multi-piece ones interleaved."""

@@ -106,10 +106,25 @@ def test_the_real_piece_and_the_widest_window():
     assert header["max_keys"] == P + 510 and 2 * header["lds_wave"] <= 64 * 1024
 
 
+@pytest.mark.parametrize("k,w", [(3, 1), (3, 4), (2, PIECE + 1)])
+def test_layout_edges(k, w):
+    edges = mc.layout_edges(k, PIECE)
+    got = run([(k, w, PIECE, sum(lens), offsets_of(lens)) for lens, _ in edges])
+    for (lens, windows), (header, pieces) in zip(edges, got):
+        want = expected_pieces(lens, k, w, PIECE)
+        assert pieces == want, lens
+        assert [sum(p["count"] for p in pieces if p["rec"] == r) for r in range(len(lens))] == windows, lens
+        cut = sum(1 for n in windows if n > PIECE)
+        assert header["npieces"] == len(lens) + cut and header["piece_rec"] == (1 if cut else 0), lens
+        assert header["max_keys"] == max(p["hi"] - p["lo"] for p in want) <= PIECE + 2 * (w - 1), lens
+
+
 def test_refusals():
     got = run([(3, 2, PIECE, 9, [1, 9]),                # does not start at 0
                (3, 2, PIECE, 9, [0, 8]),                # does not end at nbytes
                (3, 2, PIECE, 9, [0, 6, 5, 9]),          # falls
                (3, 2, PIECE, 9, [0, 12, 9]),            # passes nbytes on the way
-               (3, 2, PIECE, 9, [0, 9])])
-    assert [g if g[0] == "refused" else "ok" for g in got] == [("refused", "ends"), ("refused", "ends"), ("refused", "rise"), ("refused", "rise"), "ok"]
+               (3, 2, PIECE, 9, [0, 9]),
+               (3, 2, PIECE, 9, [1, 12, 8])])           # starts past 0, ends before nbytes and falls: the ends are named
+    assert [g if g[0] == "refused" else "ok" for g in got] == [("refused", "ends"), ("refused", "ends"), ("refused", "rise"), ("refused", "rise"), "ok",
+                                                               ("refused", "ends")]

@@ -78,6 +78,20 @@ def _offsets(lens):
     return [sum(lens[:r]) for r in range(len(lens) + 1)]
 
 
+def _answers(cases):
+    """the program's answers to (k, continues, nbytes, offsets), each the layout computed here"""
+    commands = tuple(str(x) for k, cont, nbytes, offs in cases for x in ("score", k, PIECE, cont, nbytes, ",".join(str(o) for o in offs)))
+    lines = prog.run(commands)
+    assert len(lines) == len(cases)
+    answers = []
+    for (k, cont, nbytes, offs), line in zip(cases, lines):
+        head, _, answer = line.partition(":")
+        assert head == "score k=%d continues=%d nbytes=%d offs=%s" % (k, cont, nbytes, ",".join(str(o) for o in offs))
+        assert answer == _layout(offs, nbytes, k, bool(cont)), head
+        answers.append(answer)
+    return answers
+
+
 def test_score_layouts_and_refusals():
     cases = []                                         # (k, continues, nbytes, offsets)
     for k in (1, 3, 12):
@@ -92,17 +106,23 @@ def test_score_layouts_and_refusals():
     cases.append((3, 0, 9, [0, 4, 12, 9]))                                 # ... that pass nbytes on the way
     cases.append((3, 0, 9, [0, 4, 8]))                                     # ... that do not end at nbytes
     cases.append((3, 0, 9, [1, 4, 9]))                                     # ... that do not start at 0
-    commands = tuple(str(x) for k, cont, nbytes, offs in cases for x in ("score", k, PIECE, cont, nbytes, ",".join(str(o) for o in offs)))
-    lines = prog.run(commands)
-    assert len(lines) == len(cases)
-    for (k, cont, nbytes, offs), line in zip(cases, lines):
-        head, _, answer = line.partition(":")
-        assert head == "score k=%d continues=%d nbytes=%d offs=%s" % (k, cont, nbytes, ",".join(str(o) for o in offs))
-        assert answer == _layout(offs, nbytes, k, bool(cont)), head
     # the cases are what they say
-    answers = [_layout(offs, nbytes, k, bool(cont)) for k, cont, nbytes, offs in cases]
+    answers = _answers(cases)
     assert all(" nshort=0 npieces=12 " in a and a.endswith("piece_rec=0,1,2,3,4,5,6,7,7,8,8,8") for a in answers[:3])
     assert answers[3] == " nshort=1 npieces=3 rec_piece0=0,1,2,3 piece_rec="
     assert " nshort=1 " in answers[4] and " nshort=0 " in answers[5] and " nshort=1 " in answers[6]
     assert answers[7] == " nshort=0 npieces=3 rec_piece0=0,1,2,3 piece_rec="
     assert answers[8:] == [" error=rise", " error=rise", " error=ends", " error=ends"]
+
+
+def test_score_layout_edges():
+    k = 3
+    edges = score_cases.layout_edges(k, PIECE)
+    cases = [(k, int(cont), sum(lens), _offsets(lens)) for lens, cont, _, _ in edges]
+    cases.append((k, 0, 9, [1, 12, 8]))                                    # starts past 0, ends before nbytes and falls: the ends are named
+    answers = _answers(cases)
+    csv = lambda v: ",".join(str(x) for x in v)
+    for (lens, cont, nshort, pieces), answer in zip(edges, answers):
+        piece_rec = [r for r, n in enumerate(pieces) for _ in range(n)] if nshort == 0 and max(pieces) > 1 else []
+        assert answer == " nshort=%d npieces=%d rec_piece0=%s piece_rec=%s" % (nshort, sum(pieces), csv(_offsets(pieces)), csv(piece_rec)), lens
+    assert answers[-1] == " error=ends"

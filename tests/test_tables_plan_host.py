@@ -106,6 +106,19 @@ def test_single_piece_batches_have_no_piece_rec_and_short_records_are_rows_of_th
     assert [(p["count"], p["at"]) for p in a] == [(4, 0), (4, 12)] and [(p["count"], p["at"]) for p in b] == [(3, 2), (4, 12)]
 
 
+@pytest.mark.parametrize("stride", [1, 2, 3])
+def test_layout_edges(stride):
+    k = 3
+    edges = tc.layout_edges(k, stride, PIECE)
+    got = run([(k, stride, phase, PIECE, 1 << 31, sum(lens), offsets_of(lens)) for lens, phase, _ in edges])
+    for (lens, phase, windows), (header, pieces) in zip(edges, got):
+        want, multi = expected_pieces(lens, k, stride, phase, PIECE)
+        assert pieces == want, (lens, phase)
+        assert [sum(p["count"] for p in pieces if p["rec"] == r) for r in range(len(lens))] == windows, (lens, phase)
+        assert multi == [r for r, n in enumerate(windows) if n > PIECE]
+        assert header == {"npieces": str(len(lens) + len(multi)), "multi": ",".join(str(r) for r in multi), "piece_rec": "1" if multi else "0"}
+
+
 def test_refusals():
     got = run([(3, 3, 0, PIECE, 1 << 31, 9, [1, 9]),                # does not start at 0
                (3, 3, 0, PIECE, 1 << 31, 9, [0, 8]),                # does not end at nbytes
@@ -114,6 +127,10 @@ def test_refusals():
                (6, 1, 0, PIECE, 1 << 13, 0, [0, 0, 0]),             # 2 x 4^6 entries, 2^13 allowed: the cap is met
                (6, 1, 0, PIECE, 1 << 13, 0, [0, 0, 0, 0]),          # ... and passed
                (1, 1, 0, PIECE, 7, 0, [0, 0]),
-               (1, 1, 0, PIECE, 7, 0, [0, 0, 0])])
+               (1, 1, 0, PIECE, 7, 0, [0, 0, 0]),
+               (3, 3, 0, PIECE, 1 << 31, 9, [1, 12, 8]),            # starts past 0, ends before nbytes and falls: the ends are named
+               (1, 1, 0, PIECE, 7, 0, [0, 1, 0, 0]),                # rises past nbytes, and too many entries: the offsets are named
+               (1, 1, 0, PIECE, 7, 0, [0, 0, 0, 1])])
     assert [g if g[0] == "refused" else "ok" for g in got] == [("refused", "ends"), ("refused", "ends"), ("refused", "rise"), ("refused", "rise"), "ok",
-                                                               ("refused", "entries"), "ok", ("refused", "entries")]
+                                                               ("refused", "entries"), "ok", ("refused", "entries"), ("refused", "ends"),
+                                                               ("refused", "rise"), ("refused", "ends")]
