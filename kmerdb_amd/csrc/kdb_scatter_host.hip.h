@@ -12,7 +12,7 @@ namespace kdb {
 // k = 17).  Level 2 of the two-level path existed at k = 13 only to split one more bit pair: 4.48 -> see DESIGN.md section 5.
 constexpr int SC1_THREADS = 1024, SC1_RINGS = 1024, SC1_GRID = 256, SC1_K = 13;
 
-// tuning options of the paged paths (engine options of the same meaning: kdb_engine.hip, the option table)
+// tuning options of the paged paths (engine options of the same meaning: kdb_engine_options.hip.h, the option table)
 struct PagedOptions {
     int grid = 0;                          // persistent workgroups (0 = SC_GRID)
     int lo_bits = 0;                       // id bits below the bucket field; 0 = SC_LO_BITS_ONE_LEVEL / _TWO_LEVEL (SC_LO_BITS_MAX: buckets from the leading id bits, uneven in canonical mode)
@@ -861,5 +861,52 @@ inline int twolevel_paged_count(TwoLevelPaged &tp, const PagedOptions &opt, hipS
     }
     return 0;
 }
+
+#ifdef KDB_SC_PROF
+// What the scatter kernels of a -DKDB_SC_PROF build have stamped since the last report (kdb_sync calls it with the device idle): their
+// wave-cycles by phase, and when the workgroups of each kernel's last launch ended (KDB_SC_WG_DUMP=file: every workgroup's); to stderr.
+inline void sc_prof_report()
+{
+    unsigned long long h[32];
+    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_sc_prof), sizeof h) != hipSuccess || !(h[8] || h[24])) return;
+    static const char *names[8] = {"ids", "requests+stage-next+writes", "barrier 1", "flush", "barrier 2", "drain", "flush: word, page turn, line list", "flush: list read, line read, store"};
+    static const char *kern[2] = {"scatter_bases_kernel", "scatter_ids_kernel"};
+    for (int s2 = 0; s2 < 2; s2++) {
+        const unsigned long long *g = h + 16 * s2;
+        if (!g[8]) continue;
+        unsigned long long tot = 0;
+        for (int q = 0; q < 8; q++) tot += g[q];
+        fprintf(stderr, "[sc_prof] %s: %llu workgroups; wave-cycles by phase:", kern[s2], g[8]);
+        for (int q = 0; q < 8; q++) fprintf(stderr, " %s %.1f%%", names[q], 100.0 * (double)g[q] / (double)tot);
+        fprintf(stderr, " | total %.3g wave-cycles\n", (double)tot);
+    }
+    memset(h, 0, sizeof h);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sc_prof), h, sizeof h);
+    // the last launch of each kernel: when its workgroups ended, relative to the launch's span
+    static unsigned long long wg[2][2][1024];
+    if (hipMemcpyFromSymbol(wg, HIP_SYMBOL(g_sc_wg), sizeof wg) != hipSuccess) return;
+    for (int s2 = 0; s2 < 2; s2++) {
+        std::vector<unsigned long long> st, en;
+        for (int w = 0; w < 1024; w++) if (wg[s2][1][w]) { st.push_back(wg[s2][0][w]); en.push_back(wg[s2][1][w]); }
+        if (en.empty()) continue;
+        const unsigned long long t00 = *std::min_element(st.begin(), st.end()), t11 = *std::max_element(en.begin(), en.end());
+        if (const char *dump = getenv("KDB_SC_WG_DUMP")) {
+            if (FILE *f = fopen(dump, "a")) {
+                fprintf(f, "%s", kern[s2]);
+                for (size_t w = 0; w < en.size(); w++) fprintf(f, " %.4f", (double)(en[w] - t00) / (double)(t11 - t00));
+                fprintf(f, "\n");
+                fclose(f);
+            }
+        }
+        std::sort(en.begin(), en.end());
+        const double t0 = (double)t00, span = (double)t11 - t0;
+        fprintf(stderr, "[sc_prof] %s, last launch: %zu workgroups, %.0f us; ends at min %.1f%% p10 %.1f%% p50 %.1f%% p90 %.1f%% of it\n", kern[s2], en.size(), span / 100.0,
+                100.0 * ((double)en.front() - t0) / span, 100.0 * ((double)en[en.size() / 10] - t0) / span, 100.0 * ((double)en[en.size() / 2] - t0) / span,
+                100.0 * ((double)en[en.size() * 9 / 10] - t0) / span);
+    }
+    memset(wg, 0, sizeof wg);
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_sc_wg), wg, sizeof wg);
+}
+#endif
 
 }  // namespace kdb

@@ -3,7 +3,7 @@ op sequences over that life, and a driver that runs a sequence on anything with 
 against the model.  No GPU and no torch at import: tests/test_lifecycle_model_cpu.py checks the model and the driver against an
 oracle-backed stand-in, tests/test_gpu_lifecycle.py runs the same sequences on the real engine.
 
-The engine carries host-side state from batch to batch (kdb_engine.hip, kdb_scatter_host.hip.h): whether the deferred histogram pass
+The engine carries host-side state from batch to batch (kdb_engine.hip, kdb_engine_options.hip.h, kdb_scatter_host.hip.h): whether the deferred histogram pass
 may STORE a bucket's histogram over the vector or must ADD to it, batches pending in the page arena, records staged but not counted,
 sticky error words.  None of it shows in a job that creates an engine, submits, reads once and closes; it shows in sequences."""
 import numpy as np
@@ -291,9 +291,9 @@ def draw_sequence(rng, k, two_level_13=True):
 
 
 def pending_before(ops, k):
-    """For each op: how many batches the two-level path holds in its page arena when the op begins, by the rules of kdb_engine.hip
-    (None where the arena's size makes that unpredictable: arena_batches below its default).  A batch is pending after a submit at
-    k > one_level_max_k under algo 2 with defer_flush 1 and no device-side accumulation of host submits; a sync, a read, a fold, a reset
+    """For each op: how many batches the two-level path holds in its page arena when the op begins, by the rules of kdb_engine.hip and
+    kdb_engine_options.hip.h (None where the arena's size makes that unpredictable: arena_batches below its default).  A batch is pending
+    after a submit at k > one_level_max_k under algo 2 with defer_flush 1 and no device-side accumulation of host submits; a sync, a read, a fold, a reset
     and a change of sc_lo_bits / one_level_max_k / defer_flush = 0 leave none."""
     opt = {"algo": 2, "defer_flush": 1, "one_level_max_k": 13, "accum_bytes": -1, "arena_batches": 8}
     small_stage = any(o["op"] == "set_option" and o["name"] in ("stage_bytes", "stage_reads") for o in ops)     # a submit is then many device batches

@@ -72,7 +72,8 @@ def test_uniform_window_ids_and_the_same_residues_with_marks(gpu_engine_cls, k):
 @pytest.mark.parametrize("k", ALL_K)
 def test_single_record_shred_and_its_scratch(gpu_engine_cls, oracle, k):
     """kdb_shred (no offsets: resolve_suspects_kernel's one-record form, no lens / mark kernels) on records of k .. 2 T + 9
-    residues with N's; one engine takes a large record, a small one, then a larger one: shred_scratch is reused, then grown."""
+    residues with N's; one engine takes a large record, a small one, then a larger one: the scratch of window_ids_run (kdb_engine.hip) is
+    reused, then grown."""
     from kmerdb_amd.engine import IdsEngine
     rest = [L for L in ic.single_lengths(k) if L not in (T, k, 2 * T + 9)]
     for canon in (True, False):

@@ -347,6 +347,39 @@ def test_continuation_pieces_through_every_submit_path(gpu_engine_cls, oracle, k
                         del t
 
 
+def test_the_edges_of_the_submit_cut_at_the_smallest_staging_buffer(gpu_engine_cls, oracle):
+    """The edge list of tests/submit_cases.py (the engine cuts a submit itself where a record, or a run of records, does not fit a staging
+    buffer) at the smallest real buffer: one batch through submit and submit_pinned, appended to the accumulated batch or counted
+    from the staging slot, both counting kernels; the whole vector against the oracle's, and finish()'s own Sum check."""
+    import kmerdb_amd
+    import submit_cases as sc
+    cap, max_recs, k = 4096, 3, 11
+    lengths = [k] * 4 + [cap, cap + 1, 2 * cap - (k - 1), 2 * cap - (k - 1) + 1] + [cap + 1, k, k]
+    offsets = np.array(sc.offsets_of(lengths), dtype=np.uint64)
+    pieces, refusal = sc.cut([int(o) for o in offsets], False, cap, max_recs, k)
+    shapes = [(p["nbytes"], p["nrecs"], p["cont"], p["inside"]) for p in pieces]
+    assert refusal is None and len(pieces) == 12
+    for shape in ((cap, 1, 0, 0), (cap, 1, 0, 1), (k, 1, 1, 0), (cap, 1, 1, 0), (cap, 1, 1, 1), (3 * k, 3, 0, 0), (k, 1, 0, 0), (3 * k, 3, 1, 0)):
+        assert shape in shapes, shape
+    rng = np.random.Generator(np.random.PCG64(11))
+    bases = lm.LET[rng.integers(0, 4, size=int(offsets[-1]))].copy()
+    tile = next(p for p in pieces if p["inside"])
+    bases[[tile["start"] - 3, tile["start"] + cap - 6]] = ord("N")      # in a whole piece; in the k - 1 bytes a tile and the piece behind it share
+    want, want_total = oracle.c_count(bases, offsets, k, True, oracle.N_DROP)
+    pinned = kmerdb_amd.pinned_empty(bases.size)
+    pinned[:] = bases
+    for algo in (1, 2):
+        for src in (bases, pinned):
+            for accum in (0, 1 << 20):
+                with gpu_engine_cls(k, algo=algo) as eng:
+                    for name, value in (("stage_bytes", cap), ("stage_reads", max_recs), ("accum_bytes", accum)):
+                        eng.set_option(name, value)
+                    (eng.submit_pinned if src is pinned else eng.submit)(src, offsets)
+                    counts, total, unique = eng.finish()
+                    assert total == want_total and unique == int(np.count_nonzero(want)), (algo, src is pinned, accum)
+                    assert np.array_equal(counts, want), (algo, src is pinned, accum)
+
+
 # --------------------------------------------------------------------------------------------------------------------------------
 # 7. the fixed seeds, through the driver that the stand-in engine passed on the CPU
 # --------------------------------------------------------------------------------------------------------------------------------

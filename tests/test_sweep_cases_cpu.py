@@ -18,8 +18,10 @@ TOP = sc.TOP
 WIDE = 2 ** 32
 
 
-# the files that hold the host code of the analysis sweeps: the entry points, their plans, and the engine they left
-HOST_FILES = ("kdb_analysis_host.hip.h", "kdb_sweep_plan.cpp.h", "kdb_hostutil.hip.h", "kdb_engine.hip")
+# the files that hold the host code of the analysis sweeps: the entry points, their plans, and the engine they left (with the headers its
+# host code is split into)
+HOST_FILES = ("kdb_analysis_host.hip.h", "kdb_sweep_plan.cpp.h", "kdb_hostutil.hip.h", "kdb_engine.hip", "kdb_io_abi.hip.h", "kdb_probe_host.hip.h",
+              "kdb_engine_options.hip.h", "kdb_submit_plan.cpp.h")
 
 
 def _host_rows():
