@@ -478,7 +478,8 @@ int kdb_minimizers(int device_id, int k, int w, int canonical, int order,
 
 /*
  * A batch of independent banded local alignments with affine gaps (csrc/kdb_align.hip.h): the extend step of
- * seed-and-extend, for the seeds kdb_minimizers gives.  Per task the score and the four end coordinates; no traceback, no CIGAR.
+ * seed-and-extend, for the seeds kdb_minimizers gives.  Per task the score and the four end coordinates; the path between them, as
+ * CIGAR runs, is kdb_align_traceback's, below.
  * The reference's `alignment` subcommand (kmerdb/__init__.py:454-573) exits before it aligns; its score arguments are kept, nothing else.
  * Query record x is q_bases[q_offsets[x] .. q_offsets[x + 1]), reference record y likewise in r_bases.  Task t aligns query task_q[t] to
  * reference task_r[t]:
@@ -521,6 +522,50 @@ int kdb_align_banded(int device_id,
                      int band, int match, int mismatch, int gap_open, int gap_extend,
                      int32_t *score_out, uint32_t *qstart_out, uint32_t *qend_out, uint32_t *rstart_out, uint32_t *rend_out /* ntasks each */,
                      double *kernel_ms_out /* may be NULL */);
+
+/*
+ * The same batch of alignments with their paths (csrc/kdb_align_trace.hip.h): what kdb_align_banded reports and, per
+ * task, the run-length encoded alignment from the origin to the best cell.  The records, the tasks, band and the scores are
+ * kdb_align_banded's, and so is everything in its comment: oriented query, band, s(i, j), H / E / F, tie rules, best cell.  The five
+ * scalar outputs are bit-equal to kdb_align_banded's on the same arguments.
+ * THE TRACEBACK is the walk those tie rules imply.  Start at the best cell in state H.
+ *   state H at (i, j): if H took the diagonal term (the first of [diagonal, E, F] that reaches its value): emit `=` if Q[i] = R[j] and both
+ *     are one of A, C, G, T, else `X`; if H(i - 1, j - 1) = 0, or there is no such cell, stop; otherwise continue in state H at
+ *     (i - 1, j - 1).  If H took E: go to state E at (i, j) and emit nothing.  Otherwise go to state F at (i, j) and emit nothing.
+ *   state E at (i, j): emit `D` (R[j] is against a gap).  If H(i, j - 1) + gap_open >= E(i, j - 1) + gap_extend continue in state H at
+ *     (i, j - 1), otherwise in state E at (i, j - 1).
+ *   state F at (i, j): emit `I`.  If H(i - 1, j) + gap_open >= F(i - 1, j) + gap_extend continue in state H at (i - 1, j), otherwise in
+ *     state F at (i - 1, j).
+ * The emitted ops are reversed and run-length encoded; equal neighbours merge (two separate gaps of one kind can only abut where
+ * gap_open > gap_extend, and then read as one run).  A run is one uint32, (len << 4) | op, with BAM's op codes I = 1, D = 2, `=` = 7,
+ * X = 8.  A task without a positive score has no runs.  What follows from the definition: the walk stops exactly at the origin
+ * (qstart, rstart); the runs consume qend - qstart query residues (=, X, I) and rend - rstart reference residues (=, X, D); match per =,
+ * mismatch per X and gap_open + (len - 1) max(gap_open, gap_extend) per gap run add up to the score; a task has at most
+ * (qend - qstart) + (rend - rstart) runs.
+ * nruns_out[t]: the runs of task t; they are runs_out[S_t .. S_t + nruns_out[t]), S the exclusive prefix sums of nruns_out, in alignment
+ * order from the origin to the end cell.  The cap protocol is kdb_minimizers': the five scalars, nruns_out and *total_out (the sum of
+ * nruns_out) are written whenever the status is KDB_OK; runs_out, which holds cap entries, only if *total_out <= cap; cap = 0 with
+ * runs_out = NULL asks for the sizes alone.
+ * All are exact integers and do not depend on the grid, on the other tasks, on the task's place among them or on scratch_limit.
+ * SCRATCH: the forward pass leaves 4 bits per cell -- where H came from (2 bits) and whether the E and the F the cell hands on opened or
+ * extended --, 64 bytes per anti-diagonal step of a task whatever the band, in whole groups of 4 steps: about 11 KB for 150 residues at
+ * band 16, 67 MB for 2^20.  The call works through its tasks in chunks of consecutive tasks: a chunk is the longest run of tasks whose
+ * directions fit scratch_limit bytes (0: KDB_ALIGN_TRACE_SCRATCH, 2 GiB -- a choice, not a measurement) and holds at least one task.
+ * Limits and errors as kdb_align_banded, all settled on the host before anything is launched, and no output is written on a refusal;
+ * also KDB_ERR_ARG: nruns_out or total_out NULL, runs_out NULL where cap > 0.  KDB_ERR_NOMEM: the scratch -- the largest chunk's
+ * directions, cap runs -- does not fit.  ntasks = 0: KDB_OK and *total_out = 0 once the scalars are in range.  kernel_ms_out (may be
+ * NULL): device time of all kernels of all chunks, by HIP events.
+ */
+#define KDB_ALIGN_TRACE_SCRATCH 2147483648ull
+int kdb_align_traceback(int device_id,
+                        const uint8_t *q_bases, size_t q_nbytes, const uint64_t *q_offsets, size_t nq,
+                        const uint8_t *r_bases, size_t r_nbytes, const uint64_t *r_offsets, size_t nr,
+                        const uint32_t *task_q, const uint32_t *task_r, const int64_t *task_diag, const uint8_t *task_strand, size_t ntasks,
+                        int band, int match, int mismatch, int gap_open, int gap_extend,
+                        size_t scratch_limit,
+                        int32_t *score_out, uint32_t *qstart_out, uint32_t *qend_out, uint32_t *rstart_out, uint32_t *rend_out /* ntasks each */,
+                        uint64_t *nruns_out /* ntasks */, uint32_t *runs_out, size_t cap, uint64_t *total_out,
+                        double *kernel_ms_out /* may be NULL */);
 
 /*
  * Host-side record splitter (no GPU work): what Bio.SeqIO.parse does for kmerdb/parse.py:50-85 on this path.

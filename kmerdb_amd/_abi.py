@@ -28,6 +28,7 @@ KDB_SCORE_CONTINUES, KDB_SCORE_PIECE, KDB_SCORE_LANES = 1, 2048, 64
 KDB_TABLES_CONTINUES, KDB_TABLES_PIECE, KDB_TABLES_MAX_K = 1, 8192, 6
 KDB_MINIMIZER_LEX, KDB_MINIMIZER_HASHED, KDB_MINIMIZER_MAX_K, KDB_MINIMIZER_MAX_W, KDB_MINIMIZER_PIECE = 0, 1, 31, 256, 2048
 KDB_ALIGN_MAX_BAND, KDB_ALIGN_MAX_QUERY, KDB_ALIGN_STAGE, KDB_ALIGN_GRID_MAX = 63, 1 << 20, 512, 4096
+KDB_ALIGN_TRACE_SCRATCH = 1 << 31
 ABI_VERSION = 6
 
 # every symbol include/kdbhip.h declares: (name, restype, argtypes)
@@ -82,6 +83,9 @@ SYMBOLS = (
     ("kdb_align_banded", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp,
                                         ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp, _vp,
                                         ctypes.POINTER(ctypes.c_double)]),
+    ("kdb_align_traceback", ctypes.c_int, [ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp,
+                                           ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_size_t, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp, ctypes.c_size_t, _vp, ctypes.POINTER(ctypes.c_double)]),
     ("kdb_parse_fastq",ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp,
                                        ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     ("kdb_parse_fastq_mt", ctypes.c_int, [_vp, ctypes.c_size_t, ctypes.c_int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp,

@@ -2,7 +2,9 @@
 csrc/kdb_align.hip.h).
 
 align_tasks is the device call on a batch of tasks: per task a query record, a reference record, the diagonal the band is centred on
-and the query's strand -> the best local score with affine gaps inside the band and where that alignment begins and ends.  seed_tasks
+and the query's strand -> the best local score with affine gaps inside the band and where that alignment begins and ends;
+align_tasks_cigar (kdb_align_traceback, csrc/kdb_align_trace.hip.h) also gives the path between the two as
+run-length encoded CIGAR runs, which cigar_string and cigar_nm turn into a SAM CIGAR and its NM.  seed_tasks
 turns the minimizer sketches of the queries and of the reference (minimizer.minimizers, on the device) into such tasks, in plain numpy;
 finish_tasks turns the call's output into per-query result lists; align_file does all of it for a reference and a query file, and
 align_table prints its results (the `alignment` subcommand).  The reference's `alignment` (kmerdb/__init__.py:454-573) exits before it
@@ -105,6 +107,85 @@ def align_tasks(q_bases, q_offsets, r_bases, r_offsets, task_q, task_r, task_dia
     return align_raw(q_bases, q_offsets, r_bases, r_offsets, task_q, task_r, task_diag, task_strand, band, match, mismatch, gap_open, gap_extend, device)[:5]
 
 
+# ---- the traceback ----
+
+OP_I, OP_D, OP_EQ, OP_X = 1, 2, 7, 8           # BAM's op codes; a run is (len << 4) | op
+_OP_CHAR = {OP_I: "I", OP_D: "D", OP_EQ: "=", OP_X: "X"}
+RUNS_GUESS = 16                                # runs per task the lists are sized for at the first call
+
+
+def traceback_raw(q_bases, q_offsets, r_bases, r_offsets, task_q, task_r, task_diag, task_strand, band, match, mismatch, gap_open, gap_extend, cap, scratch_limit=0,
+                  device=0):
+    """kdb_align_traceback on checked arguments, the run list sized for `cap` runs -> (score, qstart, qend, rstart, rend, nruns: uint64[t],
+    runs: uint32[total] or None where total > cap, total, kernel_ms)"""
+    n = int(task_q.size)
+    score = np.zeros(n, dtype=np.int32)
+    qstart, qend, rstart, rend = (np.zeros(n, dtype=np.uint32) for _ in range(4))
+    nruns, runs = np.zeros(n, dtype=np.uint64), np.empty(cap, dtype=np.uint32)
+    total, ms = ctypes.c_uint64(0), ctypes.c_double(0.0)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    _abi.check(_abi.lib().kdb_align_traceback(int(device), ptr(q_bases), int(q_bases.size), q_offsets.ctypes.data, int(q_offsets.size) - 1, ptr(r_bases),
+                                              int(r_bases.size), r_offsets.ctypes.data, int(r_offsets.size) - 1, ptr(task_q), ptr(task_r), ptr(task_diag),
+                                              ptr(task_strand), n, band, match, mismatch, gap_open, gap_extend, int(scratch_limit), ptr(score), ptr(qstart),
+                                              ptr(qend), ptr(rstart), ptr(rend), ptr(nruns), ptr(runs), cap, ctypes.byref(total), ctypes.byref(ms)))
+    t = int(total.value)
+    return score, qstart, qend, rstart, rend, nruns, (runs[:t] if t <= cap else None), t, ms.value
+
+
+def _traceback(args, cap, scratch_limit, device):
+    """size, then fill: the lists sized for `cap` runs, and once more with the total where that is not enough -> traceback_raw's tuple"""
+    out = traceback_raw(*args, cap, scratch_limit, device)
+    if out[6] is None:
+        first = out[7]
+        out = traceback_raw(*args, first, scratch_limit, device)
+        if out[6] is None:
+            raise _abi.KdbHipError("kdb_align_traceback: two calls on one batch found {0} and {1} runs".format(first, out[7]))
+    return out
+
+
+def align_tasks_cigar(q_bases, q_offsets, r_bases, r_offsets, task_q, task_r, task_diag, task_strand, band=16, match=3, mismatch=-1, gap_open=-10, gap_extend=-1,
+                      device=0, scratch_limit=None):
+    """align_tasks with the alignments' paths -> (score, qstart, qend, rstart, rend, nruns: uint64[t], runs: uint32[sum of nruns]).
+
+    The five first are align_tasks' own.  Task t's runs are runs[S_t : S_t + nruns[t]], S the exclusive prefix sums of nruns, from the
+    alignment's origin to its end: a run is (len << 4) | op with BAM's op codes I = 1 (a query residue against a gap), D = 2 (a reference
+    residue against one), `=` = 7 and X = 8.  The walk that gives them is include/kdbhip.h's.  scratch_limit: the bytes of direction
+    scratch per chunk of tasks (None: KDB_ALIGN_TRACE_SCRATCH); the result does not depend on it."""
+    band, match, mismatch, gap_open, gap_extend = _check_scores(band, match, mismatch, gap_open, gap_extend)
+    q_bases, q_offsets = _check_records("q", q_bases, q_offsets)
+    r_bases, r_offsets = _check_records("r", r_bases, r_offsets)
+    task_q, task_r, task_diag, task_strand = _check_tasks(task_q, task_r, task_diag, task_strand, q_offsets, int(r_offsets.size) - 1)
+    scratch_limit = 0 if scratch_limit is None else _int("scratch_limit", scratch_limit, 1, (1 << 63) - 1)
+    from .distance import _require_device
+    _require_device(device)
+    args = (q_bases, q_offsets, r_bases, r_offsets, task_q, task_r, task_diag, task_strand, band, match, mismatch, gap_open, gap_extend)
+    return _traceback(args, RUNS_GUESS * int(task_q.size), scratch_limit, device)[:7]
+
+
+def cigar_string(runs, qstart, qend, m, eqx=False):
+    """A task's runs as a SAM CIGAR of its oriented query of m residues: qstart S first and m - qend S last (none of length 0); eqx: `=`
+    and X as they are, else merged into M."""
+    ops = []
+    if qstart:
+        ops.append([int(qstart), "S"])
+    for run in np.asarray(runs).tolist():
+        ch = _OP_CHAR[run & 15]
+        if not eqx and ch in "=X":
+            ch = "M"
+        if ops and ops[-1][1] == ch and ch != "S":
+            ops[-1][0] += run >> 4
+        else:
+            ops.append([run >> 4, ch])
+    if m - qend:
+        ops.append([int(m - qend), "S"])
+    return "".join("{0}{1}".format(n, ch) for n, ch in ops)
+
+
+def cigar_nm(runs):
+    """the edit distance of the aligned part: the lengths of the X, I and D runs"""
+    return sum(run >> 4 for run in np.asarray(runs).tolist() if run & 15 in (OP_X, OP_I, OP_D))
+
+
 # ---- seeding: plain numpy on the two sketches ----
 
 def _check_seeding(k, w, order, min_seeds, max_occ, max_candidates, min_score):
@@ -176,11 +257,11 @@ def seed_tasks(sketch, q_lens, q_counts, q_ids, q_pos, q_strand, k, band, min_se
     return g_query[top].astype(np.uint32), g_ref[top].astype(np.uint32), median[top], g_rel[top].astype(np.uint8), hits[top]
 
 
-def finish_tasks(nq, q_lens, tasks, out, min_score=0):
+def finish_tasks(nq, q_lens, tasks, out, min_score=0, with_task=False):
     """The results of every query, from its tasks (by query and rank, as seed_tasks gives them) and the device's output for them
     -> a list per query of (qstart, qend, rel, ref, rstart, rend, score, seeds, diag), query coordinates on the query's own strand.
     Without the tasks that found nothing or less than min_score and without a result that repeats a better-ranked one of its query in
-    (ref, rel, all four coordinates); by (-score, ref, rel, rstart)."""
+    (ref, rel, all four coordinates); by (-score, ref, rel, rstart).  with_task: every result has the index of its task behind it."""
     task_q, task_r, task_diag, task_strand, seeds = tasks
     score, qstart, qend, rstart, rend = out
     results = [[] for _ in range(nq)]
@@ -191,7 +272,7 @@ def finish_tasks(nq, q_lens, tasks, out, min_score=0):
             a, b = m - b, m - a
         found = (a, b, rel, int(task_r[t]), int(rstart[t]), int(rend[t]), int(score[t]), int(seeds[t]), int(task_diag[t]))
         if not any(x[:6] == found[:6] for x in results[q]):                    # (the tasks come by rank: the better-ranked one is there already)
-            results[q].append(found)
+            results[q].append(found + (t,) if with_task else found)
     for found in results:
         found.sort(key=lambda x: (-x[6], x[3], x[2], x[4]))                   # (stable: of equal keys the better-ranked stays first)
     return results
@@ -202,8 +283,10 @@ def _sketch_of(bases, offsets, k, w, order, device):
 
 
 def align_records(sketch, r_bases, r_offsets, q_bases, q_offsets, k, w, order, band, match, mismatch, gap_open, gap_extend, min_seeds, max_candidates, min_score,
-                  device=0, times=None):
-    """one batch of queries against a built sketch -> finish_tasks' lists.  times: a dict that collects the seconds of each part"""
+                  device=0, times=None, cigar=False, eqx=False):
+    """one batch of queries against a built sketch -> finish_tasks' lists.  times: a dict that collects the seconds of each part.
+    cigar: the device call is the traceback's, and every result has its CIGAR string -- along the oriented query, as SAM has it -- and its
+    NM behind it"""
     import time
     t0 = time.perf_counter()
     q_lens = np.diff(q_offsets.astype(np.int64))
@@ -214,9 +297,22 @@ def align_records(sketch, r_bases, r_offsets, q_bases, q_offsets, k, w, order, b
     t1 = time.perf_counter()
     tasks = seed_tasks(sketch, q_lens, q_counts, q_ids, q_pos, q_strand, k, band, min_seeds, max_candidates)
     t2 = time.perf_counter()
-    out = align_raw(q_bases, q_offsets, r_bases, r_offsets, tasks[0], tasks[1], tasks[2], tasks[3], band, match, mismatch, gap_open, gap_extend, device)
+    args = (q_bases, q_offsets, r_bases, r_offsets, tasks[0], tasks[1], tasks[2], tasks[3], band, match, mismatch, gap_open, gap_extend)
+    if cigar:
+        traced = _traceback(args, RUNS_GUESS * int(tasks[0].size), 0, device)
+        out = traced[:5] + (traced[8],)
+    else:
+        out = align_raw(*args, device)
     t3 = time.perf_counter()
-    results = finish_tasks(int(q_lens.size), q_lens, tasks, out[:5], min_score)
+    results = finish_tasks(int(q_lens.size), q_lens, tasks, out[:5], min_score, with_task=cigar)
+    if cigar:
+        nruns, runs = traced[5].astype(np.int64), traced[6]
+        ends = np.cumsum(nruns)
+        for q, found in enumerate(results):
+            for x, result in enumerate(found):
+                t = result[-1]
+                mine = runs[int(ends[t] - nruns[t]):int(ends[t])]
+                found[x] = result[:-1] + (cigar_string(mine, int(out[1][t]), int(out[2][t]), int(q_lens[q]), eqx), cigar_nm(mine))
     t4 = time.perf_counter()
     if times is not None:
         for name, dt in (("sketching", t1 - t0), ("seeding", t2 - t1 + t4 - t3), ("device", t3 - t2)):
@@ -227,12 +323,13 @@ def align_records(sketch, r_bases, r_offsets, q_bases, q_offsets, k, w, order, b
 
 
 def align_file(reference, query, k=15, w=10, order="hashed", band=16, match=3, mismatch=-1, gap_open=-10, gap_extend=-1, min_seeds=2, max_occ=50,
-               max_candidates=4, min_score=0, best_only=False, device=0, batch_residues=None, times=None):
+               max_candidates=4, min_score=0, best_only=False, device=0, batch_residues=None, times=None, cigar=False, eqx=False):
     """Every query record of a FASTA/FASTQ file against the records of a reference FASTA: yields, per query in file order and per result
     by (-score, ref, rel, rstart), (qname, qlen, qstart, qend, strand, rname, rlen, rstart, rend, score, seeds, diag) -- the alignment
     covers [qstart, qend) of the query as the file has it and [rstart, rend) of the reference record; strand 1: the query's reverse
     complement is what aligns; seeds: the minimizer hits of the candidate, diag: the diagonal its band was centred on.  best_only: the
-    first result of every query alone.  The reference is read whole, the query in batches."""
+    first result of every query alone.  The reference is read whole, the query in batches.  cigar: two more fields, the alignment's
+    CIGAR (soft clips included; strand 1: along the reverse-complemented query, as SAM has it; eqx: `=` and X, not M) and its NM."""
     from . import reader
     if type(reference) is not str or type(query) is not str:
         raise TypeError("kmerdb_amd.alignment.align_file expects the reference and the query file as str filepaths")
@@ -262,11 +359,11 @@ def align_file(reference, query, k=15, w=10, order="hashed", band=16, match=3, m
             q_bases = np.ascontiguousarray(bases[int(offsets[a]):int(offsets[b])])
             q_offsets = (offsets[a:b + 1] - offsets[a]).astype(np.uint64)
             results = align_records(sketch, r_bases, r_offsets, q_bases, q_offsets, k, w, order, band, match, mismatch, gap_open, gap_extend, min_seeds,
-                                    max_candidates, min_score, device, times)
+                                    max_candidates, min_score, device, times, cigar, eqx)
             for q, found in enumerate(results):
                 qname, qlen = str(ids[a + q]), int(offsets[a + q + 1] - offsets[a + q])
-                for qstart, qend, rel, ref, rstart, rend, score, seeds, diag in (found[:1] if best_only else found):
-                    yield (qname, qlen, qstart, qend, rel, r_names[ref], int(r_lens[ref]), rstart, rend, score, seeds, diag)
+                for qstart, qend, rel, ref, rstart, rend, score, seeds, diag, *path in (found[:1] if best_only else found):
+                    yield (qname, qlen, qstart, qend, rel, r_names[ref], int(r_lens[ref]), rstart, rend, score, seeds, diag, *path)
             a = b
 
 

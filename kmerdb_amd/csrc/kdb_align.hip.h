@@ -1,5 +1,6 @@
 // kdb_align.hip.h -- a batch of banded local alignments with affine gaps (kdb_align_banded of include/kdbhip.h):
-// per task the best score and where that alignment begins and ends in the oriented query and in the reference record.  No traceback.
+// per task the best score and where that alignment begins and ends in the oriented query and in the reference record.  The traceback
+// (kdb_align_traceback) is kdb_align_trace.hip.h: its forward pass is this one, with the direction stores switched on.
 //
 // One wave owns one task from its first row to its last; the waves stride through the tasks.  With jb = d - band a cell (i, j) lies on the
 // band's diagonal c = j - i - jb, 0 <= c <= 2 band <= 126, and lane l owns the diagonals 2l and 2l + 1.  The wave sweeps anti-diagonals:
@@ -79,15 +80,19 @@ __device__ __forceinline__ uint32_t inside4(uint32_t codes, int64_t p, int64_t l
 
 // One cell.  In: H, oH = H(i - 1, c) and its origin; (e, oe) and (f, of) = E(i, c) and F(i, c) as the neighbours left them; s = s(i, j);
 // here = this cell as an origin.  Out: H, oH = H(i, c); (Ec, oEc), (Fc, oFc) = what the right and the lower neighbour take.
-// The origin of a value that is not positive is never used and may be anything.
+// The origin of a value that is not positive is never used and may be anything.  dir: the cell's four direction bits for the traceback
+// (kdb_align_trace.hip.h) -- bits 0-1 where H comes from (DIR_START: the diagonal from H = 0, DIR_DIAG, DIR_E, DIR_F), DIR_E_OPENS and
+// DIR_F_OPENS where the Ec and the Fc it hands on take the H + gap_open term; a caller that does not keep them pays nothing for them.
+constexpr uint32_t DIR_START = 0, DIR_DIAG = 1, DIR_E = 2, DIR_F = 3, DIR_E_OPENS = 4, DIR_F_OPENS = 8;
 __device__ __forceinline__ void cell(int &H, uint32_t &oH, int e, uint32_t oe, int f, uint32_t of, int s, uint32_t here, int gap_open, int gap_extend, bool in_band,
-                                     int &Ec, uint32_t &oEc, int &Fc, uint32_t &oFc)
+                                     int &Ec, uint32_t &oEc, int &Fc, uint32_t &oFc, uint32_t &dir)
 {
     const uint32_t od = H == 0 ? here : oH;                                   // a diagonal step from H = 0, or from nothing, starts here
     const int dg = H + s;
     const int h = max(max(dg, e), max(f, 0));
     const uint32_t o = dg == h ? od : (e == h ? oe : of);                      // the first of [diagonal, E, F] that reaches h
     const int ho = h + gap_open, ee = e + gap_extend, ff = f + gap_extend;
+    dir = (dg == h ? (H == 0 ? DIR_START : DIR_DIAG) : (e == h ? DIR_E : DIR_F)) | (ho >= ee ? DIR_E_OPENS : 0u) | (ho >= ff ? DIR_F_OPENS : 0u);
     H = in_band ? h : 0;
     oH = o;
     Ec = in_band ? max(ho, ee) : NEG;
@@ -96,14 +101,17 @@ __device__ __forceinline__ void cell(int &H, uint32_t &oH, int e, uint32_t oe, i
     oFc = ho >= ff ? o : of;
 }
 
-// grid: at most GRID_MAX workgroups of WAVES waves, WAVES * align_lds_wave(STAGE) bytes of dynamic LDS.  q_words / r_words: the two residue
-// buffers as aligned words (the call's own allocations), q_nwords / r_nwords of them.
-__global__ void __launch_bounds__(TPB)
-align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint64_t *__restrict__ q_offs, const uint32_t *__restrict__ r_words, int64_t r_nwords,
-             const uint64_t *__restrict__ r_offs, const uint32_t *__restrict__ task_q, const uint32_t *__restrict__ task_r, const int64_t *__restrict__ task_diag,
-             const uint8_t *__restrict__ task_strand, uint32_t ntasks, int band, int match, int mismatch, int gap_open, int gap_extend,
-             int32_t *__restrict__ score_out, uint32_t *__restrict__ qstart_out, uint32_t *__restrict__ qend_out, uint32_t *__restrict__ rstart_out,
-             uint32_t *__restrict__ rend_out)
+// The forward pass of the tasks [task_lo, task_hi), the waves striding through them.  q_words / r_words: the two residue buffers as aligned
+// words (the call's own allocations), q_nwords / r_nwords of them.  TRACE: every lane also stores the direction bits of its eight cells
+// of a group as one dword -- nibble 2 r + (c & 1) for the group's row r -- at kdbplan::align_trace_dword(group, lane) of the task's bytes,
+// which begin dir_offs[task] bytes into dirs (kdbplan::align_trace_chunks).
+template <bool TRACE>
+__device__ __forceinline__ void
+align_tasks(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint64_t *__restrict__ q_offs, const uint32_t *__restrict__ r_words, int64_t r_nwords,
+            const uint64_t *__restrict__ r_offs, const uint32_t *__restrict__ task_q, const uint32_t *__restrict__ task_r, const int64_t *__restrict__ task_diag,
+            const uint8_t *__restrict__ task_strand, uint32_t task_lo, uint32_t task_hi, int band, int match, int mismatch, int gap_open, int gap_extend,
+            int32_t *__restrict__ score_out, uint32_t *__restrict__ qstart_out, uint32_t *__restrict__ qend_out, uint32_t *__restrict__ rstart_out,
+            uint32_t *__restrict__ rend_out, uint32_t *__restrict__ dirs, const uint64_t *__restrict__ dir_offs)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     const int lane = (int)(threadIdx.x & 63u);
@@ -113,7 +121,7 @@ align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint6
     uint32_t *const r_lds = q_lds + LDS_Q / 4;
     const bool even_in = 2 * lane <= 2 * band, odd_in = 2 * lane + 1 <= 2 * band;
 
-    for (uint32_t task = __builtin_amdgcn_readfirstlane(blockIdx.x * WAVES + wave); task < ntasks; task += gridDim.x * WAVES) {   // (wave-uniform)
+    for (uint32_t task = __builtin_amdgcn_readfirstlane(task_lo + blockIdx.x * WAVES + wave); task < task_hi; task += gridDim.x * WAVES) {   // (wave-uniform)
         const uint32_t tq = task_q[task], tr = task_r[task];
         const bool minus = task_strand[task] != 0;
         const int64_t q0 = (int64_t)q_offs[tq], r0 = (int64_t)r_offs[tr];
@@ -133,6 +141,7 @@ align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint6
         uint32_t oHe = 0, oHo = 0, oEcE = 0, oFcE = 0, oEcO = 0, oFcO = 0;
         int best = 0;
         uint32_t best_at = 0, best_from = 0;
+        uint32_t *const task_dirs = TRACE ? dirs + dir_offs[task] / 4 : nullptr;
 
         for (int ts = t_lo; ts < t_hi; ts += (int)STAGE) {
             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");            // the last stage's reads before this one's writes
@@ -159,6 +168,7 @@ align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint6
                 const uint32_t x = (uint32_t)(t0 - ts) + BACK - (uint32_t)lane, y = x + 2u * (uint32_t)lane;
                 const uint32_t qw = __builtin_amdgcn_alignbyte(q_lds[x / 4 + 1], q_lds[x / 4], x & 3u);
                 const u64 rw = (((u64)r_lds[y / 4 + 1] << 32) | r_lds[y / 4]) >> (8u * (y & 3u));
+                uint32_t group_dirs = 0, dir;
 #pragma unroll
                 for (int r = 0; r < (int)kdbplan::ALIGN_GROUP; r++) {
                     const int i = t0 + r - lane;
@@ -168,14 +178,17 @@ align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint6
                     int e = __shfl_up(EcO, 1);
                     const uint32_t oe = __shfl_up(oEcO, 1);
                     if (lane == 0) e = NEG;                                   // (the diagonal c = -1 is outside the band)
-                    cell(He, oHe, e, oe, FcO, oFcO, q == re ? match : mismatch, here, gap_open, gap_extend, even_in, EcE, oEcE, FcE, oFcE);
+                    cell(He, oHe, e, oe, FcO, oFcO, q == re ? match : mismatch, here, gap_open, gap_extend, even_in, EcE, oEcE, FcE, oFcE, dir);
+                    if (TRACE) group_dirs |= dir << (8 * r);
                     if (He > best && i < lim_even) { best = He; best_at = here; best_from = oHe; }
                     // odd half: E from the own even cell, F from lane + 1's even cell (lane 63's odd diagonal is never in the band)
                     const int f = __shfl_down(FcE, 1);
                     const uint32_t of = __shfl_down(oFcE, 1);
-                    cell(Ho, oHo, EcE, oEcE, f, of, q == ro ? match : mismatch, here | 1u, gap_open, gap_extend, odd_in, EcO, oEcO, FcO, oFcO);
+                    cell(Ho, oHo, EcE, oEcE, f, of, q == ro ? match : mismatch, here | 1u, gap_open, gap_extend, odd_in, EcO, oEcO, FcO, oFcO, dir);
+                    if (TRACE) group_dirs |= dir << (8 * r + 4);
                     if (Ho > best && i < lim_odd) { best = Ho; best_at = here | 1u; best_from = oHo; }
                 }
+                if (TRACE) task_dirs[kdbplan::align_trace_dword((uint32_t)(t0 - t_lo) / kdbplan::ALIGN_GROUP, (uint32_t)lane)] = group_dirs;   // (256 bytes per wave)
             }
         }
 
@@ -201,6 +214,18 @@ align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint6
             rend_out[task] = found ? (uint32_t)(i + c + jb + 1) : 0u;
         }
     }
+}
+
+// grid: at most GRID_MAX workgroups of WAVES waves, WAVES * align_lds_wave(STAGE) bytes of dynamic LDS.  kdb_align_banded: no direction stores.
+__global__ void __launch_bounds__(TPB)
+align_kernel(const uint32_t *__restrict__ q_words, int64_t q_nwords, const uint64_t *__restrict__ q_offs, const uint32_t *__restrict__ r_words, int64_t r_nwords,
+             const uint64_t *__restrict__ r_offs, const uint32_t *__restrict__ task_q, const uint32_t *__restrict__ task_r, const int64_t *__restrict__ task_diag,
+             const uint8_t *__restrict__ task_strand, uint32_t ntasks, int band, int match, int mismatch, int gap_open, int gap_extend,
+             int32_t *__restrict__ score_out, uint32_t *__restrict__ qstart_out, uint32_t *__restrict__ qend_out, uint32_t *__restrict__ rstart_out,
+             uint32_t *__restrict__ rend_out)
+{
+    align_tasks<false>(q_words, q_nwords, q_offs, r_words, r_nwords, r_offs, task_q, task_r, task_diag, task_strand, 0u, ntasks, band, match, mismatch, gap_open, gap_extend,
+                       score_out, qstart_out, qend_out, rstart_out, rend_out, nullptr, nullptr);
 }
 
 }  // namespace kdbalign

@@ -1,9 +1,10 @@
 // kdb_analysis_host.hip.h -- host side of the analysis calls of include/kdbhip.h, the ones that take finished vectors and no kdb_engine:
 // kdb_gram, kdb_pairstats, kdb_pairfloat, kdb_size_factors, kdb_scale_counts, kdb_spectrum, kdb_rank_transform, kdb_strand_merge,
-// kdb_score_reads, and kdb_record_tables, kdb_minimizers and kdb_align_banded (which take residues alone).  Every call works in an AnalysisCall: its own stream, events and
+// kdb_score_reads, and kdb_record_tables, kdb_minimizers, kdb_align_banded and kdb_align_traceback (which take residues alone).  Every call works in an AnalysisCall: its own stream, events and
 // scratch, gone when it returns.  What the host alone decides -- rows, groups, grids, pieces -- is kdb_sweep_plan.cpp.h's.  The three calls that
 // take residues and record offsets (kdb_score_reads, kdb_record_tables, kdb_minimizers) check them with record_check_args / record_check_sizes
-// and bring them and their kdbplan::RecordLayout to the device through one RecordBatch; kdb_align_banded stages its word-padded buffers itself.
+// and bring them and their kdbplan::RecordLayout to the device through one RecordBatch; kdb_align_banded and kdb_align_traceback share
+// their checks (align_check_scalars, align_check_batch) and stage their word-padded buffers through one AlignBatch.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,7 @@
 #include "kdb_tables.hip.h"
 #include "kdb_minimizers.hip.h"
 #include "kdb_align.hip.h"
+#include "kdb_align_trace.hip.h"
 #include "kdb_sweep_plan.cpp.h"
 
 namespace {
@@ -819,73 +821,225 @@ int kdb_minimizers(int device_id, int k, int w, int canonical, int order, const 
     return KDB_OK;
 }
 
-// ---- banded local alignments, a wave per task (kdb_align.hip.h) ----
+// ---- banded local alignments, a wave per task (kdb_align.hip.h), and their traceback (kdb_align_trace.hip.h) ----
+}  // extern "C"
+
+namespace {
+
+// what kdb_align_banded and kdb_align_traceback take alike
+struct AlignArgs {
+    const uint8_t *q_bases;
+    size_t q_nbytes;
+    const uint64_t *q_offs;
+    size_t nq;
+    const uint8_t *r_bases;
+    size_t r_nbytes;
+    const uint64_t *r_offs;
+    size_t nr;
+    const uint32_t *task_q, *task_r;
+    const int64_t *task_diag;
+    const uint8_t *task_strand;
+    size_t ntasks;
+    int band, match, mismatch, gap_open, gap_extend;
+    int32_t *score_out;
+    uint32_t *qstart_out, *qend_out, *rstart_out, *rend_out;
+};
+
+int align_check_scalars(const char *who, const AlignArgs &a)
+{
+    if (a.band < 1 || a.band > kdbalign::MAX_BAND) return fail(KDB_ERR_ARG, "%s: band=%d out of range 1..%d", who, a.band, kdbalign::MAX_BAND);
+    if (a.match < 1 || a.match > 127) return fail(KDB_ERR_ARG, "%s: match=%d out of range 1..127", who, a.match);
+    if (a.mismatch < -127 || a.mismatch > 0 || a.gap_open < -127 || a.gap_open > 0 || a.gap_extend < -127 || a.gap_extend > 0)
+        return fail(KDB_ERR_ARG, "%s: mismatch=%d, gap_open=%d, gap_extend=%d: each must lie in -127..0", who, a.mismatch, a.gap_open, a.gap_extend);
+    return KDB_OK;
+}
+
+// everything about a batch of ntasks >= 1 tasks that is settled on the host: every address the kernels form (the offsets and the tasks
+// are host memory) and every residue
+int align_check_batch(const char *who, const AlignArgs &a, kdbplan::AlignLayout &lay)
+{
+    namespace ka = kdbalign;
+    if (!a.q_offs || !a.r_offs || (!a.q_bases && a.q_nbytes) || (!a.r_bases && a.r_nbytes) || !a.task_q || !a.task_r || !a.task_diag || !a.task_strand || !a.score_out ||
+        !a.qstart_out || !a.qend_out || !a.rstart_out || !a.rend_out)
+        return fail(KDB_ERR_ARG, "%s: NULL buffer", who);
+    if (a.q_nbytes > (1ull << 30) || a.r_nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "%s: at most 2^30 residues per buffer", who);
+    if (a.nq > (1ull << 30) || a.nr > (1ull << 30)) return fail(KDB_ERR_ARG, "%s: at most 2^30 records per buffer", who);
+    if (a.ntasks > (1ull << 26)) return fail(KDB_ERR_ARG, "%s: at most 2^26 tasks per call", who);
+    if (const kdbplan::LayoutError bad = kdbplan::align_layout(a.q_offs, a.nq, a.q_nbytes, a.r_offs, a.nr, a.r_nbytes, a.task_q, a.task_r, a.task_diag, a.task_strand,
+                                                               a.ntasks, (uint32_t)a.band, ka::MAX_QUERY, ka::WAVES, ka::GRID_MAX, lay)) {
+        if (bad == kdbplan::LAYOUT_ENDS) return fail(KDB_ERR_ARG, "%s: offsets must start at 0 and end at the buffer's size", who);
+        if (bad == kdbplan::LAYOUT_RISE) return fail(KDB_ERR_ARG, "%s: offsets must rise from 0 to the buffer's size", who);
+        if (bad == kdbplan::LAYOUT_TASK) return fail(KDB_ERR_ARG, "%s: task %llu names a record that is not there", who, (unsigned long long)lay.bad);
+        if (bad == kdbplan::LAYOUT_STRAND) return fail(KDB_ERR_ARG, "%s: task %llu has a strand that is neither 0 nor 1", who, (unsigned long long)lay.bad);
+        return fail(KDB_ERR_ARG, "%s: the query of task %llu holds more than 2^20 residues", who, (unsigned long long)lay.bad);
+    }
+    // so are the residues: every byte is one of ACGTN, or nothing is launched
+    if (const uint64_t nbad = residues_outside_acgtn(a.q_bases, a.q_nbytes) + residues_outside_acgtn(a.r_bases, a.r_nbytes))
+        return fail(KDB_ERR_BAD_RESIDUE, "%s: %llu residue(s) outside ACGTN", who, (unsigned long long)nbad);
+    return KDB_OK;
+}
+
+// the batch on the device: the residues as whole words, the offsets, the tasks and the five outputs per task
+struct AlignBatch {
+    uint64_t q_nwords = 0, r_nwords = 0;
+    uint32_t *q = nullptr, *r = nullptr, *tq = nullptr, *tr = nullptr, *out = nullptr;
+    uint64_t *qoffs = nullptr, *roffs = nullptr;
+    int64_t *diag = nullptr;
+    uint8_t *strand = nullptr;
+
+    bool alloc(AnalysisCall &call, const AlignArgs &a)
+    {
+        q_nwords = (a.q_nbytes + 3) / 4, r_nwords = (a.r_nbytes + 3) / 4;                            // (the kernels read whole words, and none outside these)
+        q = call.alloc<uint32_t>(q_nwords + 4), r = call.alloc<uint32_t>(r_nwords + 4);
+        qoffs = call.alloc<uint64_t>(a.nq + 1), roffs = call.alloc<uint64_t>(a.nr + 1);
+        tq = call.alloc<uint32_t>(a.ntasks), tr = call.alloc<uint32_t>(a.ntasks);
+        diag = call.alloc<int64_t>(a.ntasks);
+        strand = call.alloc<uint8_t>(a.ntasks);
+        out = call.alloc<uint32_t>(5 * (uint64_t)a.ntasks);
+        return q && r && qoffs && roffs && tq && tr && diag && strand && out;
+    }
+    int upload(AnalysisCall &call, const AlignArgs &a)
+    {
+        if (a.q_nbytes) HIP_TRY(hipMemcpyAsync(q, a.q_bases, a.q_nbytes, hipMemcpyHostToDevice, call.st));
+        if (a.r_nbytes) HIP_TRY(hipMemcpyAsync(r, a.r_bases, a.r_nbytes, hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(qoffs, a.q_offs, (a.nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(roffs, a.r_offs, (a.nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(tq, a.task_q, a.ntasks * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(tr, a.task_r, a.ntasks * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(diag, a.task_diag, a.ntasks * sizeof(int64_t), hipMemcpyHostToDevice, call.st));
+        HIP_TRY(hipMemcpyAsync(strand, a.task_strand, a.ntasks, hipMemcpyHostToDevice, call.st));
+        return KDB_OK;
+    }
+    uint32_t *column(const AlignArgs &a, int x) const { return out + (uint64_t)x * a.ntasks; }       // score, qstart, qend, rstart, rend
+    int download(AnalysisCall &call, const AlignArgs &a)
+    {
+        HIP_TRY(hipMemcpyAsync(a.score_out, column(a, 0), a.ntasks * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
+        HIP_TRY(hipMemcpyAsync(a.qstart_out, column(a, 1), a.ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        HIP_TRY(hipMemcpyAsync(a.qend_out, column(a, 2), a.ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        HIP_TRY(hipMemcpyAsync(a.rstart_out, column(a, 3), a.ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        HIP_TRY(hipMemcpyAsync(a.rend_out, column(a, 4), a.ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+        return KDB_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
 int kdb_align_banded(int device_id, const uint8_t *q_bases, size_t q_nbytes, const uint64_t *q_offs, size_t nq, const uint8_t *r_bases, size_t r_nbytes,
                      const uint64_t *r_offs, size_t nr, const uint32_t *task_q, const uint32_t *task_r, const int64_t *task_diag, const uint8_t *task_strand,
                      size_t ntasks, int band, int match, int mismatch, int gap_open, int gap_extend, int32_t *score_out, uint32_t *qstart_out, uint32_t *qend_out,
                      uint32_t *rstart_out, uint32_t *rend_out, double *kernel_ms_out)
 {
     namespace ka = kdbalign;
+    const char *const who = "kdb_align_banded";
+    const AlignArgs a{q_bases, q_nbytes, q_offs, nq, r_bases, r_nbytes, r_offs, nr, task_q, task_r, task_diag, task_strand, ntasks, band, match, mismatch, gap_open,
+                      gap_extend, score_out, qstart_out, qend_out, rstart_out, rend_out};
     if (kernel_ms_out) *kernel_ms_out = 0.0;
-    if (band < 1 || band > ka::MAX_BAND) return fail(KDB_ERR_ARG, "kdb_align_banded: band=%d out of range 1..%d", band, ka::MAX_BAND);
-    if (match < 1 || match > 127) return fail(KDB_ERR_ARG, "kdb_align_banded: match=%d out of range 1..127", match);
-    if (mismatch < -127 || mismatch > 0 || gap_open < -127 || gap_open > 0 || gap_extend < -127 || gap_extend > 0)
-        return fail(KDB_ERR_ARG, "kdb_align_banded: mismatch=%d, gap_open=%d, gap_extend=%d: each must lie in -127..0", mismatch, gap_open, gap_extend);
+    if (int rc = align_check_scalars(who, a)) return rc;
     if (ntasks == 0) return KDB_OK;
-    if (!q_offs || !r_offs || (!q_bases && q_nbytes) || (!r_bases && r_nbytes) || !task_q || !task_r || !task_diag || !task_strand || !score_out || !qstart_out ||
-        !qend_out || !rstart_out || !rend_out)
-        return fail(KDB_ERR_ARG, "kdb_align_banded: NULL buffer");
-    if (q_nbytes > (1ull << 30) || r_nbytes > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_align_banded: at most 2^30 residues per buffer");
-    if (nq > (1ull << 30) || nr > (1ull << 30)) return fail(KDB_ERR_ARG, "kdb_align_banded: at most 2^30 records per buffer");
-    if (ntasks > (1ull << 26)) return fail(KDB_ERR_ARG, "kdb_align_banded: at most 2^26 tasks per call");
-    // every address the kernel forms is settled here: the offsets and the tasks are host memory
     kdbplan::AlignLayout lay;
-    if (const kdbplan::LayoutError bad = kdbplan::align_layout(q_offs, nq, q_nbytes, r_offs, nr, r_nbytes, task_q, task_r, task_diag, task_strand, ntasks, (uint32_t)band,
-                                                               ka::MAX_QUERY, ka::WAVES, ka::GRID_MAX, lay)) {
-        if (bad == kdbplan::LAYOUT_ENDS) return fail(KDB_ERR_ARG, "kdb_align_banded: offsets must start at 0 and end at the buffer's size");
-        if (bad == kdbplan::LAYOUT_RISE) return fail(KDB_ERR_ARG, "kdb_align_banded: offsets must rise from 0 to the buffer's size");
-        if (bad == kdbplan::LAYOUT_TASK) return fail(KDB_ERR_ARG, "kdb_align_banded: task %llu names a record that is not there", (unsigned long long)lay.bad);
-        if (bad == kdbplan::LAYOUT_STRAND) return fail(KDB_ERR_ARG, "kdb_align_banded: task %llu has a strand that is neither 0 nor 1", (unsigned long long)lay.bad);
-        return fail(KDB_ERR_ARG, "kdb_align_banded: the query of task %llu holds more than 2^20 residues", (unsigned long long)lay.bad);
-    }
-    // so are the residues: every byte is one of ACGTN, or nothing is launched
-    if (const uint64_t nbad = residues_outside_acgtn(q_bases, q_nbytes) + residues_outside_acgtn(r_bases, r_nbytes))
-        return fail(KDB_ERR_BAD_RESIDUE, "kdb_align_banded: %llu residue(s) outside ACGTN", (unsigned long long)nbad);
+    if (int rc = align_check_batch(who, a, lay)) return rc;
     AnalysisCall call;
     if (int rc = call.open(device_id)) return rc;
 
-    const uint64_t q_nwords = (q_nbytes + 3) / 4, r_nwords = (r_nbytes + 3) / 4;                 // (the kernel reads whole words, and none outside these)
-    auto *d_q = call.alloc<uint32_t>(q_nwords + 4), *d_r = call.alloc<uint32_t>(r_nwords + 4);
-    auto *d_qoffs = call.alloc<uint64_t>(nq + 1), *d_roffs = call.alloc<uint64_t>(nr + 1);
-    auto *d_tq = call.alloc<uint32_t>(ntasks), *d_tr = call.alloc<uint32_t>(ntasks);
-    auto *d_diag = call.alloc<int64_t>(ntasks);
-    auto *d_strand = call.alloc<uint8_t>(ntasks);
-    auto *d_out = call.alloc<uint32_t>(5 * (uint64_t)ntasks);
-    if (!d_q || !d_r || !d_qoffs || !d_roffs || !d_tq || !d_tr || !d_diag || !d_strand || !d_out)
-        return fail(KDB_ERR_NOMEM, "kdb_align_banded: no room for %zu + %zu residues and %zu tasks", q_nbytes, r_nbytes, ntasks);
-    if (q_nbytes) HIP_TRY(hipMemcpyAsync(d_q, q_bases, q_nbytes, hipMemcpyHostToDevice, call.st));
-    if (r_nbytes) HIP_TRY(hipMemcpyAsync(d_r, r_bases, r_nbytes, hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_qoffs, q_offs, (nq + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_roffs, r_offs, (nr + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_tq, task_q, ntasks * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_tr, task_r, ntasks * sizeof(uint32_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_diag, task_diag, ntasks * sizeof(int64_t), hipMemcpyHostToDevice, call.st));
-    HIP_TRY(hipMemcpyAsync(d_strand, task_strand, ntasks, hipMemcpyHostToDevice, call.st));
-    uint32_t *o_score = d_out, *o_qs = d_out + ntasks, *o_qe = d_out + 2 * ntasks, *o_rs = d_out + 3 * ntasks, *o_re = d_out + 4 * ntasks;
+    AlignBatch in;
+    if (!in.alloc(call, a)) return fail(KDB_ERR_NOMEM, "%s: no room for %zu + %zu residues and %zu tasks", who, q_nbytes, r_nbytes, ntasks);
+    if (int rc = in.upload(call, a)) return rc;
     HIP_TRY(call.begin());
-    hipLaunchKernelGGL(ka::align_kernel, dim3(lay.grid), dim3(ka::TPB), (size_t)ka::WAVES * kdbplan::align_lds_wave(ka::STAGE), call.st, (const uint32_t *)d_q,
-                       (int64_t)q_nwords, (const uint64_t *)d_qoffs, (const uint32_t *)d_r, (int64_t)r_nwords, (const uint64_t *)d_roffs, (const uint32_t *)d_tq,
-                       (const uint32_t *)d_tr, (const int64_t *)d_diag, (const uint8_t *)d_strand, (uint32_t)ntasks, band, match, mismatch, gap_open, gap_extend,
-                       (int32_t *)o_score, o_qs, o_qe, o_rs, o_re);
+    hipLaunchKernelGGL(ka::align_kernel, dim3(lay.grid), dim3(ka::TPB), (size_t)ka::WAVES * kdbplan::align_lds_wave(ka::STAGE), call.st, (const uint32_t *)in.q,
+                       (int64_t)in.q_nwords, (const uint64_t *)in.qoffs, (const uint32_t *)in.r, (int64_t)in.r_nwords, (const uint64_t *)in.roffs, (const uint32_t *)in.tq,
+                       (const uint32_t *)in.tr, (const int64_t *)in.diag, (const uint8_t *)in.strand, (uint32_t)ntasks, band, match, mismatch, gap_open, gap_extend,
+                       (int32_t *)in.column(a, 0), in.column(a, 1), in.column(a, 2), in.column(a, 3), in.column(a, 4));
     HIP_TRY(hipGetLastError());
     HIP_TRY(call.end());
-    HIP_TRY(hipMemcpyAsync(score_out, o_score, ntasks * sizeof(int32_t), hipMemcpyDeviceToHost, call.st));
-    HIP_TRY(hipMemcpyAsync(qstart_out, o_qs, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
-    HIP_TRY(hipMemcpyAsync(qend_out, o_qe, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
-    HIP_TRY(hipMemcpyAsync(rstart_out, o_rs, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
-    HIP_TRY(hipMemcpyAsync(rend_out, o_re, ntasks * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    if (int rc = in.download(call, a)) return rc;
     HIP_TRY(hipStreamSynchronize(call.st));
     HIP_TRY(call.elapsed(kernel_ms_out));
+    return KDB_OK;
+}
+
+int kdb_align_traceback(int device_id, const uint8_t *q_bases, size_t q_nbytes, const uint64_t *q_offs, size_t nq, const uint8_t *r_bases, size_t r_nbytes,
+                        const uint64_t *r_offs, size_t nr, const uint32_t *task_q, const uint32_t *task_r, const int64_t *task_diag, const uint8_t *task_strand,
+                        size_t ntasks, int band, int match, int mismatch, int gap_open, int gap_extend, size_t scratch_limit, int32_t *score_out, uint32_t *qstart_out,
+                        uint32_t *qend_out, uint32_t *rstart_out, uint32_t *rend_out, uint64_t *nruns_out, uint32_t *runs_out, size_t cap, uint64_t *total_out,
+                        double *kernel_ms_out)
+{
+    namespace ka = kdbalign;
+    const char *const who = "kdb_align_traceback";
+    const AlignArgs a{q_bases, q_nbytes, q_offs, nq, r_bases, r_nbytes, r_offs, nr, task_q, task_r, task_diag, task_strand, ntasks, band, match, mismatch, gap_open,
+                      gap_extend, score_out, qstart_out, qend_out, rstart_out, rend_out};
+    if (kernel_ms_out) *kernel_ms_out = 0.0;
+    if (int rc = align_check_scalars(who, a)) return rc;
+    if (!total_out) return fail(KDB_ERR_ARG, "%s: total_out must not be NULL", who);
+    if (cap > 0 && !runs_out) return fail(KDB_ERR_ARG, "%s: runs_out must not be NULL where cap > 0", who);
+    if (ntasks == 0) {
+        *total_out = 0;
+        return KDB_OK;
+    }
+    if (!nruns_out) return fail(KDB_ERR_ARG, "%s: NULL buffer", who);
+    kdbplan::AlignLayout lay;
+    if (int rc = align_check_batch(who, a, lay)) return rc;
+    // the direction scratch of every task and the chunks the call works through, on the host as well
+    std::vector<uint64_t> task_bytes(ntasks);
+    for (size_t t = 0; t < ntasks; t++) {
+        const uint64_t m = q_offs[task_q[t] + 1] - q_offs[task_q[t]], n = r_offs[task_r[t] + 1] - r_offs[task_r[t]];
+        task_bytes[t] = kdbplan::align_trace_bytes(kdbplan::align_window(m, n, task_diag[t], (uint32_t)band), (uint32_t)band);
+    }
+    kdbplan::AlignTraceChunks chunks;
+    kdbplan::align_trace_chunks(task_bytes.data(), ntasks, scratch_limit ? (uint64_t)scratch_limit : (uint64_t)KDB_ALIGN_TRACE_SCRATCH, chunks);
+    AnalysisCall call;
+    if (int rc = call.open(device_id)) return rc;
+
+    AlignBatch in;
+    const bool staged = in.alloc(call, a);
+    const uint32_t scan_blocks = (uint32_t)((ntasks + ka::SCAN_BLOCK - 1) / ka::SCAN_BLOCK);
+    auto *dirs = call.alloc<uint32_t>(chunks.largest / 4 + 1);
+    auto *dir_offs = call.alloc<uint64_t>(ntasks), *run_offs = call.alloc<uint64_t>(ntasks), *counts64 = call.alloc<uint64_t>(ntasks);
+    auto *sums = call.alloc<uint64_t>((uint64_t)scan_blocks + 1);             // (the last entry is the carry from chunk to chunk, at the end the total)
+    auto *counts = call.alloc<uint32_t>(ntasks);
+    auto *runs = cap ? call.alloc<uint32_t>(cap) : nullptr;
+    if (!staged || !dirs || !dir_offs || !run_offs || !counts64 || !sums || !counts || (cap && !runs))
+        return fail(KDB_ERR_NOMEM, "%s: no room for %zu + %zu residues, %zu tasks, %llu bytes of directions and %zu runs", who, q_nbytes, r_nbytes, ntasks,
+                    (unsigned long long)chunks.largest, cap);
+    if (int rc = in.upload(call, a)) return rc;
+    HIP_TRY(hipMemcpyAsync(dir_offs, chunks.offs.data(), ntasks * sizeof(uint64_t), hipMemcpyHostToDevice, call.st));
+    uint64_t *const carry = sums + scan_blocks;
+    HIP_TRY(hipMemsetAsync(carry, 0, sizeof(uint64_t), call.st));
+    const size_t lds = (size_t)ka::WAVES * kdbplan::align_lds_wave(ka::STAGE);
+    HIP_TRY(call.begin());
+    for (size_t k = 0; k + 1 < chunks.first.size(); k++) {
+        const uint32_t lo = (uint32_t)chunks.first[k], hi = (uint32_t)chunks.first[k + 1], nchunk = hi - lo;
+        const dim3 grid((unsigned)std::min<uint64_t>((nchunk + ka::WAVES - 1) / ka::WAVES, ka::GRID_MAX)), block(ka::TPB);
+        const uint32_t nblocks = (nchunk + ka::SCAN_BLOCK - 1) / ka::SCAN_BLOCK;
+#define KDB_TRACE_TASKS (const uint32_t *)in.q, (int64_t)in.q_nwords, (const uint64_t *)in.qoffs, (const uint32_t *)in.r, (int64_t)in.r_nwords, (const uint64_t *)in.roffs, \
+                        (const uint32_t *)in.tq, (const uint32_t *)in.tr, (const int64_t *)in.diag, (const uint8_t *)in.strand, lo, hi, band
+        hipLaunchKernelGGL(ka::trace_forward_kernel, grid, block, lds, call.st, KDB_TRACE_TASKS, match, mismatch, gap_open, gap_extend, (int32_t *)in.column(a, 0),
+                           in.column(a, 1), in.column(a, 2), in.column(a, 3), in.column(a, 4), dirs, (const uint64_t *)dir_offs);
+        hipLaunchKernelGGL(ka::walk_kernel<false>, grid, block, 0, call.st, KDB_TRACE_TASKS, (const int32_t *)in.column(a, 0), (const uint32_t *)in.column(a, 2),
+                           (const uint32_t *)in.column(a, 4), (const uint32_t *)dirs, (const uint64_t *)dir_offs, counts, (const ka::u64 *)nullptr, (uint32_t *)nullptr,
+                           (ka::u64)0);
+        hipLaunchKernelGGL(ka::scan_sums_kernel, dim3(nblocks), dim3(ka::SCAN_TPB), 0, call.st, (const uint32_t *)counts + lo, nchunk, (ka::u64 *)sums);
+        hipLaunchKernelGGL(ka::scan_top_kernel, dim3(1), dim3(ka::SCAN_TPB), 0, call.st, (ka::u64 *)sums, nblocks, (ka::u64 *)carry);
+        hipLaunchKernelGGL(ka::scan_apply_kernel, dim3(nblocks), dim3(ka::SCAN_TPB), 0, call.st, (const uint32_t *)counts + lo, nchunk, (const ka::u64 *)sums,
+                           (ka::u64 *)run_offs + lo, (ka::u64 *)counts64 + lo);
+        // (a task whose runs do not lie inside the cap writes none: the total then exceeds the cap, and the array is not handed out)
+        if (cap)
+            hipLaunchKernelGGL(ka::walk_kernel<true>, grid, block, 0, call.st, KDB_TRACE_TASKS, (const int32_t *)in.column(a, 0), (const uint32_t *)in.column(a, 2),
+                               (const uint32_t *)in.column(a, 4), (const uint32_t *)dirs, (const uint64_t *)dir_offs, counts, (const ka::u64 *)run_offs, runs, (ka::u64)cap);
+#undef KDB_TRACE_TASKS
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(call.end());
+    uint64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, carry, sizeof(uint64_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    HIP_TRY(call.elapsed(kernel_ms_out));
+    if (int rc = in.download(call, a)) return rc;
+    HIP_TRY(hipMemcpyAsync(nruns_out, counts64, ntasks * sizeof(uint64_t), hipMemcpyDeviceToHost, call.st));
+    if (total > 0 && total <= (uint64_t)cap) HIP_TRY(hipMemcpyAsync(runs_out, runs, (size_t)total * sizeof(uint32_t), hipMemcpyDeviceToHost, call.st));
+    HIP_TRY(hipStreamSynchronize(call.st));
+    *total_out = total;
     return KDB_OK;
 }
 

@@ -3,7 +3,8 @@
 // in which order and under which kernel instantiation (kdb_gram, kdb_pairstats, kdb_pairfloat), the grid of a sweep, the one check of record
 // offsets (check_offsets) and the one split of records into pieces (RecordLayout, record_layout) that kdb_score_reads, kdb_record_tables
 // (tests/c/tables_plan_check.cpp) and kdb_minimizers (tests/c/minimizers_plan_check.cpp) share -- each adds how many windows a record has and
-// what else it asks of its records --, and the window, the stages and the LDS of a task of kdb_align_banded (tests/c/alignment_plan_check.cpp).
+// what else it asks of its records --, and the window, the stages and the LDS of a task of kdb_align_banded (tests/c/alignment_plan_check.cpp) and the
+// direction scratch and the chunks of kdb_align_traceback (tests/c/traceback_plan_check.cpp).
 // The block size, HALF, the chunk sizes, the piece size and the stage are arguments: the kernel headers have them.
 // A row type is the kernel header's (kdbgram::Row, kdbpair::Row, kdbpair::FloatRow) or any struct of as many uint8_t fields.
 #pragma once
@@ -276,6 +277,44 @@ constexpr uint32_t align_stages(const AlignWindow &w, uint32_t band, uint32_t st
 constexpr uint32_t align_lds_q(uint32_t stage) { return stage + ALIGN_LANES + 8; }    // (+ 8: a lane reads the two aligned words around its 4 rows)
 constexpr uint32_t align_lds_r(uint32_t stage) { return stage + ALIGN_R_EXTRA; }
 constexpr uint32_t align_lds_wave(uint32_t stage) { return align_lds_q(stage) + align_lds_r(stage); }     // a multiple of 8 where stage is
+
+// kdb_align_traceback: the forward pass leaves 4 bits per cell, and a lane's two diagonals over the ALIGN_GROUP rows of a group are one
+// dword: every group of steps of [t_lo, t_hi) is ALIGN_LANES dwords, all 64 lanes' (the lanes beyond the band store theirs too: this is the
+// single place that says so).  Cell (i, c) is nibble 2 ((T - t_lo) % ALIGN_GROUP) + (c & 1) of dword align_trace_dword(..), T = i + c / 2.
+constexpr uint64_t ALIGN_TRACE_GROUP_BYTES = 4ull * ALIGN_LANES;
+constexpr uint32_t align_trace_groups(const AlignWindow &w, uint32_t band)
+{
+    return w.empty() ? 0 : (align_t_hi(w, band) - align_t_lo(w) + ALIGN_GROUP - 1) / ALIGN_GROUP;
+}
+constexpr uint64_t align_trace_bytes(const AlignWindow &w, uint32_t band) { return (uint64_t)align_trace_groups(w, band) * ALIGN_TRACE_GROUP_BYTES; }
+constexpr uint64_t align_trace_dword(uint32_t group, uint32_t lane) { return (uint64_t)group * ALIGN_LANES + lane; }     // (inside the task's bytes)
+
+// The call works through its tasks in chunks of consecutive tasks: a chunk is the longest run of tasks whose bytes fit `limit`, and holds
+// at least one task.  first: nchunks + 1 entries, chunk k is the tasks [first[k], first[k + 1]); offs[t]: where task t's bytes begin in its
+// chunk's scratch; largest: the bytes of the largest chunk.
+struct AlignTraceChunks {
+    std::vector<uint64_t> first, offs;
+    uint64_t largest = 0, bytes = 0;
+};
+
+inline void align_trace_chunks(const uint64_t *task_bytes, size_t ntasks, uint64_t limit, AlignTraceChunks &ch)
+{
+    ch = AlignTraceChunks();
+    ch.offs.resize(ntasks);
+    ch.first.push_back(0);
+    uint64_t used = 0;
+    for (size_t t = 0; t < ntasks; t++) {
+        if (t > ch.first.back() && (used > limit || task_bytes[t] > limit - used)) {     // (a task above the limit is a chunk of its own)
+            ch.first.push_back(t);
+            used = 0;
+        }
+        ch.offs[t] = used;
+        used += task_bytes[t];
+        ch.largest = std::max(ch.largest, used);
+        ch.bytes += task_bytes[t];
+    }
+    if (ntasks) ch.first.push_back(ntasks);
+}
 
 // The batch: every offset array must start at 0, end at its buffer's size and rise; every task must name a query and a reference record
 // (LAYOUT_TASK, bad = the task) and a strand 0 or 1 (LAYOUT_STRAND), and its query holds at most max_query residues (LAYOUT_QUERY).

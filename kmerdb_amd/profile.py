@@ -263,6 +263,9 @@ def build_parser():
     lp.add_argument("--max-candidates", type=int, default=4, help="candidates aligned per query")
     lp.add_argument("--min-score", type=int, default=0)
     lp.add_argument("--best-only", action="store_true", help="the best result of every query alone")
+    lp.add_argument("--cigar", action="store_true", help="two more columns, `cigar nm`: the alignment's CIGAR with soft clips, from a traceback on the device, "
+                                                          "and its edit distance")
+    lp.add_argument("--eqx", action="store_true", help="with --cigar: = and X instead of M")
     lp.add_argument("-o", "--output", default=None, help="write to this file instead of stdout")
     lp.add_argument("--device", type=int, default=0)
     lp.add_argument("reference", help="the reference, .fasta (optionally gzipped)")
@@ -317,6 +320,10 @@ def main(argv=None):
         from . import alignment
         kw = dict(k=a.k, w=a.w, order=a.order, band=a.band, match=a.match_score, mismatch=a.mismatch_score, gap_open=a.gap_open, gap_extend=a.gap_extend,
                   min_seeds=a.min_seeds, max_occ=a.max_occ, max_candidates=a.max_candidates, min_score=a.min_score, best_only=a.best_only, device=a.device)
+        if a.cigar:
+            kw.update(cigar=True, eqx=a.eqx)
+        elif a.eqx:
+            ap.error("alignment: --eqx needs --cigar")
         if a.output is None:
             alignment.align_table(a.reference, a.query, **kw)
         else:

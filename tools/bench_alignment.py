@@ -7,7 +7,11 @@
 The kernel time is kernel_ms_out, median (min-max) over --reps passes after --warmup; cells = the sum over the tasks of m (2 band + 1).
 The parent commit has no alignment: the yardstick is the numpy restatement of tests/alignment_cases.py on a sample of the same tasks,
 whose outputs must equal the call's, scaled to all of them.
-    python tools/bench_alignment.py [--short 1000000] [--long 10000] [--reads 1000000] [--reps 5] [--warmup 2] [--json out.json]
+    python tools/bench_alignment.py [--short 1000000] [--long 10000] [--reads 1000000] [--reps 5] [--warmup 2] [--json out.json] [--traceback]
+  --traceback   instead: kdb_align_traceback (csrc/kdb_align_trace.hip.h) on the short and the long workload, its passes alternating with
+           kdb_align_banded's on the same tasks in the same process -- both kernel times, their ratio, the bytes of direction scratch and
+           the chunks, runs per second, and whether the five scalars equal kdb_align_banded's and the runs of a sample the restatement's
+           of tests/traceback_cases.py
 No GPU, no number: this tool has no fallback."""
 import argparse
 import json
@@ -57,6 +61,58 @@ def write_fasta(path, bases, length, prefix):
             f.write(b"".join(b">%s%d\n%s\n" % (prefix, i, rows[i].tobytes()) for i in range(a, min(n, a + 100000))))
 
 
+def trace_plan(starts, m, n, band, limit):
+    """the direction scratch of the tasks (an oriented query of m residues on the diagonal starts[t] of a record of n) and the chunks of
+    consecutive tasks a limit cuts them into, as kdbplan::align_trace_bytes / align_trace_chunks have them -> (bytes, chunks)"""
+    jb = starts - band
+    i_lo, i_hi = np.maximum(0, -jb - 2 * band), np.minimum(m, n - jb)
+    task_bytes = np.where(i_lo < i_hi, 256 * ((i_hi + band - (i_lo // 4) * 4 + 3) // 4), 0)
+    chunks, used = 1, 0
+    for b in task_bytes.tolist():
+        if used and (used > limit or b > limit - used):
+            chunks, used = chunks + 1, 0
+        used += b
+    return int(task_bytes.sum()), chunks
+
+
+def bench_traceback(a, rng, ref, r_offsets, scores, out):
+    from kmerdb_amd import _abi, alignment
+    import traceback_cases as tc
+    for name, ntasks, length, band in (("short", a.short, 150, 16), ("long", a.long, 10000, 63)):
+        if ntasks == 0:
+            continue
+        bases, offsets, start, strand = cut_reads(rng, ref, ntasks, length)
+        tq, tr = np.arange(ntasks, dtype=np.uint32), np.zeros(ntasks, dtype=np.uint32)
+        args = (bases, offsets, ref, r_offsets, tq, tr, start, strand, band, scores["match"], scores["mismatch"], scores["gap_open"], scores["gap_extend"])
+        total = alignment.traceback_raw(*args, 0)[7]                          # the sizes alone
+        banded, traced = [], []
+        for rep in range(a.warmup + a.reps):                                  # the two calls alternate
+            plain = alignment.align_raw(*args)
+            got = alignment.traceback_raw(*args, total)
+            if rep >= a.warmup:
+                banded.append(plain[5])
+                traced.append(got[8])
+        same = all(np.array_equal(g, x) for g, x in zip(got[:5], plain[:5])) and got[7] == total == int(got[5].sum())
+        rows, ends = bases.reshape(ntasks, length), np.cumsum(got[5].astype(np.int64))
+        sample = min(a.sample, 200)                                           # (the restatement walks cell by cell)
+        pick = np.arange(0, ntasks, max(1, ntasks // sample))[:sample] if name == "short" else np.array([0])
+        for t in pick.tolist():
+            lo = max(0, int(start[t]) - 2 * band)                             # (the piece of the record the band can reach, and the diagonal inside it)
+            five, path = tc.trace(rows[t].tobytes(), ref[lo:int(start[t]) + length + 2 * band].tobytes(), int(start[t]) - lo, band, int(strand[t]), **scores)
+            five = five[:3] + (five[3] + lo, five[4] + lo) if five[0] else five
+            same = same and five == tuple(int(g[t]) for g in got[:5]) and path == got[6][int(ends[t] - got[5][t]):int(ends[t])].tolist()
+        nbytes, chunks = trace_plan(start, length, ref.size, band, _abi.KDB_ALIGN_TRACE_SCRATCH)
+        kb, kt = statistics.median(banded), statistics.median(traced)
+        run = {"workload": name + "_traceback", "tasks": ntasks, "query": length, "band": band, "banded_kernel_ms": banded, "traceback_kernel_ms": traced,
+               "traceback_over_banded": kt / kb, "direction_bytes": nbytes, "chunks": chunks, "runs": total, "runs_per_s": total / kt * 1e3,
+               "restatement_sample": int(pick.size), "same_outputs": bool(same)}
+        out["runs"].append(run)
+        print("%-5s %8d tasks of %5d bp, band %2d: kdb_align_banded kernel %s ms; kdb_align_traceback kernels %s ms = %.2f x; %.2f GB of directions in %d chunk(s); "
+              "%d runs = %.1f M runs/s; scalars equal kdb_align_banded's and the runs of %d tasks the restatement's: %s"
+              % (name, ntasks, length, band, med_range(banded), med_range(traced), kt / kb, nbytes / 1e9, chunks, total, total / kt / 1e3, pick.size, same), flush=True)
+        del bases, got, plain
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reference", type=int, default=5_000_000)
@@ -67,6 +123,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--traceback", action="store_true", help="kdb_align_traceback beside kdb_align_banded on the short and the long workload, nothing else")
     a = ap.parse_args()
     import kmerdb_amd
     from kmerdb_amd import _abi, alignment
@@ -79,6 +136,9 @@ def main():
     r_offsets = np.array([0, ref.size], dtype=np.uint64)
     out = {"reference": a.reference, "reps": a.reps, "warmup": a.warmup, "stage": _abi.KDB_ALIGN_STAGE, "runs": []}
     scores = dict(match=3, mismatch=-1, gap_open=-10, gap_extend=-1)
+    if a.traceback:
+        bench_traceback(a, rng, ref, r_offsets, scores, out)
+        a.short = a.long = a.reads = 0
 
     for name, ntasks, length, band in (("short", a.short, 150, 16), ("long", a.long, 10000, 63)):
         if ntasks == 0:
