@@ -51,6 +51,9 @@ int         kdb_device_count(int *n_out);
  * `d_table` may be NULL (engine hipMallocs and owns the vector) or a device
  * pointer to 4^k uint64 owned by the caller (e.g. a torch tensor that will be
  * handed to RCCL afterwards); it is zeroed by kdb_create either way.
+ * A caller's d_table must be 16-byte aligned (KDB_ERR_ARG otherwise): the histogram pass of the paged paths adds to the
+ * vector in 16-byte pieces, and which path counts a batch is only decided when the batch arrives.  The engine reads and
+ * writes the 4^k entries and nothing beside them.
  * 1 <= k <= 17 (4^17 * 8 B = 128 GiB; larger tables do not fit 288 GB).
  */
 int kdb_create(int k, int canonicalize, int n_mode, int device_id, void *d_table, kdb_engine **out);

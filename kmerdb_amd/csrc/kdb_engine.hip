@@ -801,6 +801,8 @@ static int new_engine(int k, const char *why_k, int canonicalize, int n_mode, in
 
 int kdb_create(int k, int canonicalize, int n_mode, int device_id, void *d_table, kdb_engine **out)
 {
+    // (the histogram pass of the paged paths moves the vector in 16-byte pieces, hist_flush_runs; which path counts a batch is decided later)
+    if (out && ((uintptr_t)d_table & 15u) != 0) { *out = nullptr; return fail(KDB_ERR_ARG, "d_table must be 16-byte aligned"); }
     kdb_engine *e = nullptr;
     const int rc = new_engine(k, " (4^k uint64 table must fit in HBM)", canonicalize, n_mode, device_id, out, &e);
     if (rc != KDB_OK) return rc;
