@@ -381,8 +381,12 @@ int kdb_window_ids(kdb_engine *e, const uint8_t *bases, size_t nbytes,
  * KDB_SCORE_CONTINUES: record 0 is the next piece of the previous call's last record: it starts with the last k-1 residues already given,
  * every one of its windows is a transition (no initial term) and it is exempt from the length check, as in kdb_submit_ex; the caller adds
  * the pieces' outputs.
+ * KDB_SCORE_NONE_SCORED, with KDB_SCORE_CONTINUES only: none of the record's pieces so far held a scored window (N all along, or fewer
+ * than k residues), so record 0's first scored window is the record's first and contributes the initial term ln c(w) - ln total'; the
+ * exemption from the length check stays.  Without it such a record's first scored window would be weighed against D(w), which the
+ * uncut record never does.  The caller knows: it adds the pieces' windows_out.
  * KDB_ERR_ARG: k outside 1..17, a NULL or misaligned pointer, total == 0, total + pseudocount 4^k or 4 pseudocount not below 2^64, offsets
- * that do not rise from 0 to nbytes, more than 2^30 residues, unknown flags.  KDB_ERR_SHORT_READ / KDB_ERR_BAD_RESIDUE: what kdb_window_ids
+ * that do not rise from 0 to nbytes, more than 2^30 residues, unknown flags, KDB_SCORE_NONE_SCORED without KDB_SCORE_CONTINUES.  KDB_ERR_SHORT_READ / KDB_ERR_BAD_RESIDUE: what kdb_window_ids
  * refuses (kmer.py:461-463; kmer.py:309 / :170), the outputs are then not written.  KDB_ERR_NOMEM: the scratch does not fit.
  * kernel_ms_out (may be NULL): device time of the residue check and the two scoring kernels, by HIP events.
  * KDB_SCORE_PIECE: windows one wave scores; a record of more windows is cut into pieces of that many, summed in piece order.
@@ -390,6 +394,7 @@ int kdb_window_ids(kdb_engine *e, const uint8_t *bases, size_t nbytes,
  * levels of the butterfly; every piece then adds two numbers to the record's sum.
  */
 #define KDB_SCORE_CONTINUES 1
+#define KDB_SCORE_NONE_SCORED 2
 #define KDB_SCORE_PIECE 2048
 #define KDB_SCORE_LANES 64
 int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, uint64_t total, uint64_t pseudocount,

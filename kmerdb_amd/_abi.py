@@ -25,6 +25,7 @@ KDB_PAIRSTATS_BLOCK, KDB_PAIRSTATS_HALF, KDB_PAIRSTATS_WG_BINS = 4, 2, 512
 KDB_PAIRFLOAT_GRID_MAX = 512
 KDB_SIZEFACTORS_WG_BINS, KDB_SIZEFACTORS_GRID_MAX = 512, 1024
 KDB_SCORE_CONTINUES, KDB_SCORE_PIECE, KDB_SCORE_LANES = 1, 2048, 64
+KDB_SCORE_NONE_SCORED = 2
 KDB_TABLES_CONTINUES, KDB_TABLES_PIECE, KDB_TABLES_MAX_K = 1, 8192, 6
 KDB_MINIMIZER_LEX, KDB_MINIMIZER_HASHED, KDB_MINIMIZER_MAX_K, KDB_MINIMIZER_MAX_W, KDB_MINIMIZER_PIECE = 0, 1, 31, 256, 2048
 KDB_ALIGN_MAX_BAND, KDB_ALIGN_MAX_QUERY, KDB_ALIGN_STAGE, KDB_ALIGN_GRID_MAX = 63, 1 << 20, 512, 4096

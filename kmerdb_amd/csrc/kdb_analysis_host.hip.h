@@ -630,7 +630,9 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
     if (kernel_ms_out) *kernel_ms_out = 0.0;
     if (k < 1 || k > 17) return fail(KDB_ERR_ARG, "kdb_score_reads: k=%d out of range 1..17", k);
     if (!d_vector || ((uintptr_t)d_vector & 15u) != 0) return fail(KDB_ERR_ARG, "kdb_score_reads: the vector is NULL or not 16-byte aligned");
-    if (flags & ~KDB_SCORE_CONTINUES) return fail(KDB_ERR_ARG, "kdb_score_reads: unknown flags %d", flags);
+    if (flags & ~(KDB_SCORE_CONTINUES | KDB_SCORE_NONE_SCORED)) return fail(KDB_ERR_ARG, "kdb_score_reads: unknown flags %d", flags);
+    if ((flags & KDB_SCORE_NONE_SCORED) && !(flags & KDB_SCORE_CONTINUES))
+        return fail(KDB_ERR_ARG, "kdb_score_reads: KDB_SCORE_NONE_SCORED needs KDB_SCORE_CONTINUES");
     if (total == 0) return fail(KDB_ERR_ARG, "kdb_score_reads: total is 0 (an empty profile gives no probabilities)");
     const uint64_t nbins = 1ull << (2 * k);
     const unsigned __int128 total2 = (unsigned __int128)total + (unsigned __int128)pseudocount * nbins;
@@ -640,6 +642,7 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
     if (nreads == 0) return KDB_OK;
     if (int rc = record_check_sizes("kdb_score_reads", nbytes, nreads)) return rc;
     const bool continues = (flags & KDB_SCORE_CONTINUES) != 0;
+    const bool scored_before = continues && !(flags & KDB_SCORE_NONE_SCORED);     // record 0's first scored window is a transition
     // the layout, and with it every address the kernels form, is settled here: the offsets are host memory
     kdbplan::ScoreLayout lay;
     if (const kdbplan::LayoutError bad = kdbplan::score_layout(offs, nreads, nbytes, k, kdbscore::PIECE, continues, lay)) return record_offsets_fail(bad);
@@ -671,7 +674,7 @@ int kdb_score_reads(int device_id, const void *d_vector, int k, int canonical, u
                        (const uint8_t *)in.bases, (const uint64_t *)in.offs, (const uint32_t *)in.piece_rec, (const uint32_t *)in.rec_piece0, (uint32_t)npieces,
                        (const unsigned long long *)d_vector, k, canonical ? 1 : 0, (unsigned long long)pseudocount, pieces);
     hipLaunchKernelGGL(kdbscore::record_kernel, dim3((unsigned)((nreads + 255) / 256)), dim3(256), 0, call.st, (const kdbscore::PieceOut *)pieces,
-                       (const uint32_t *)in.rec_piece0, (uint64_t)nreads, (double)(uint64_t)total2, continues ? 1 : 0, log10_p, ints, ints + nreads, ints + 2 * nreads);
+                       (const uint32_t *)in.rec_piece0, (uint64_t)nreads, (double)(uint64_t)total2, scored_before ? 1 : 0, log10_p, ints, ints + nreads, ints + 2 * nreads);
     HIP_TRY(hipGetLastError());
     HIP_TRY(call.end());
     HIP_TRY(hipMemcpyAsync(&c, ctr, sizeof c, hipMemcpyDeviceToHost, call.st));

@@ -63,27 +63,30 @@ def _vector_pointer(vector, k, device):
     return int(vector.data_ptr()), vector
 
 
-def score_reads_raw(pointer, k, canonical, total, pseudocount, bases, offsets, continues=False, device=0):
+def score_reads_raw(pointer, k, canonical, total, pseudocount, bases, offsets, continues=False, device=0, none_scored=False):
     """kdb_score_reads on a raw device pointer -> (log10_p, windows, zero_windows, min_count, kernel_ms)."""
     nreads = int(offsets.size) - 1
     log10_p = np.empty(nreads, dtype=np.float64)
     windows, zeros, mins = (np.empty(nreads, dtype=np.uint64) for _ in range(3))
     ms = ctypes.c_double(0.0)
+    flags = (_abi.KDB_SCORE_CONTINUES | (_abi.KDB_SCORE_NONE_SCORED if none_scored else 0)) if continues else 0
     _abi.check(_abi.lib().kdb_score_reads(int(device), ctypes.c_void_p(int(pointer)), int(k), 1 if canonical else 0, int(total), int(pseudocount),
                                           bases.ctypes.data if bases.size else None, int(bases.size), offsets.ctypes.data, nreads,
-                                          _abi.KDB_SCORE_CONTINUES if continues else 0, log10_p.ctypes.data, windows.ctypes.data, zeros.ctypes.data,
-                                          mins.ctypes.data, ctypes.byref(ms)))
+                                          flags, log10_p.ctypes.data, windows.ctypes.data, zeros.ctypes.data, mins.ctypes.data, ctypes.byref(ms)))
     return log10_p, windows, zeros, mins, ms.value
 
 
-def score_reads(bases, offsets, vector, k, canonical, total, pseudocount=0, continues=False, device=0):
+def score_reads(bases, offsets, vector, k, canonical, total, pseudocount=0, continues=False, device=0, none_scored=False):
     """Score a batch of records against a profile -> (log10_p: float64[n], windows, zero_windows, min_count: uint64[n]).
 
     bases / offsets: the concatenated residues and the nreads + 1 record offsets, as Engine.submit takes them.  vector: the 4^k counts as
     a torch int64 / uint64 tensor on `device`, or a device pointer.  total: the profile's total_kmers.  continues: record 0 is the next
-    piece of the previous call's last record (KDB_SCORE_CONTINUES).  ValueError for what the engine refuses (a record shorter than k, a
-    residue outside ACGTN); log10_p is -inf for a record with a k-mer the profile lacks (pseudocount 0), nan for one without a scored window."""
+    piece of the previous call's last record (KDB_SCORE_CONTINUES); none_scored, with continues: no piece of that record has held a scored
+    window so far, so its first one here is the record's first and takes the initial term (KDB_SCORE_NONE_SCORED).
+    ValueError for what the engine refuses (a record shorter than k, a residue outside ACGTN); log10_p is -inf for a record with a k-mer the profile lacks (pseudocount 0), nan for one without a scored window."""
     k, total, pseudocount = _check_scalars(k, total, pseudocount)
+    if none_scored and not continues:
+        raise ValueError("kmerdb_amd.probability: none_scored is for a record that continues the previous call's last one")
     bases, offsets = _records.check_batch("probability", bases, offsets)
     pointer, keep = _vector_pointer(vector, k, device)
     from .distance import _require_device
@@ -91,7 +94,7 @@ def score_reads(bases, offsets, vector, k, canonical, total, pseudocount=0, cont
     if keep is not None:
         import torch
         torch.cuda.synchronize(int(device))               # (the upload, or whatever produced the tensor: the call runs on a stream of its own)
-    out = score_reads_raw(pointer, k, canonical, total, pseudocount, bases, offsets, continues, device)[:4]
+    out = score_reads_raw(pointer, k, canonical, total, pseudocount, bases, offsets, continues, device, none_scored)[:4]
     del keep
     return out
 
@@ -167,7 +170,8 @@ def score_file(seqfile, kdb_path, pseudocount=0, device=0, block_bytes=None):
     """Every record of a FASTA/FASTQ file against a .kdb profile: yields (id, length, windows, zero_windows, min_count, log10_p,
     log_odds_ratio) per record, in file order.  k, the totals and whether the profile is canonical come from the .kdb; its counts are
     uploaded once.  A FASTA record longer than a reader block arrives in pieces that repeat k - 1 residues: they are scored with
-    KDB_SCORE_CONTINUES and joined here -- windows and zero_windows added, the minimum of min_count, log10_p added in piece order."""
+    KDB_SCORE_CONTINUES (and KDB_SCORE_NONE_SCORED while the record has no scored window yet) and joined here -- windows and zero_windows
+    added, the minimum of min_count, log10_p added in piece order."""
     from . import reader
     if type(seqfile) is not str or type(kdb_path) is not str:
         raise TypeError("kmerdb_amd.probability.score_file expects the sequence file and the .kdb as str filepaths")
@@ -179,7 +183,9 @@ def score_file(seqfile, kdb_path, pseudocount=0, device=0, block_bytes=None):
     for block in rd:
         bases, offsets, ids = block
         cont = bool(getattr(block, "cont", False))
-        log10_p, windows, zeros, mins = score_reads(bases, offsets, vector, k, canonical, total, pseudocount, continues=cont, device=device)
+        # (a record whose pieces so far hold no scored window -- an N run longer than a block -- still owes its initial term)
+        log10_p, windows, zeros, mins = score_reads(bases, offsets, vector, k, canonical, total, pseudocount, continues=cont, device=device,
+                                                    none_scored=cont and pending is not None and pending.windows == 0)
         lens = np.diff(offsets.astype(np.int64))
         first = 0
         if cont and pending is not None:

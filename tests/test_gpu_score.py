@@ -289,6 +289,66 @@ def test_a_long_record_cut_into_continuation_pieces_joins(dev, k):
     assert int(got[1][0]) == 0 and math.isnan(got[0][0]) and int(got[1][1]) == len([w for w in sc.window_ids(whole[:k + 3], k) if w is not None])
 
 
+@pytest.mark.parametrize("k", [1, 4, 9])
+def test_a_first_piece_without_a_scored_window_leaves_the_initial_term_to_the_next(dev, k):
+    """A record that begins with Ns (or with fewer than k clean residues) and is cut inside them: no window of the first piece is scored,
+    so the first scored window of the continuing piece is the record's first and is weighed against total', not against D(w).
+    KDB_SCORE_NONE_SCORED says so; without it the join is off by ln D(w) - ln total', far outside the bound.  (Found by the seeded
+    run of tests/fuzz_records.py: seed 202, case 11 of the score call.)"""
+    from kmerdb_amd import _abi, probability
+    rng = np.random.default_rng(190 + k)
+    body = sc.random_record(rng, PIECE + 300, p_n=0.001)
+    v, total = sc.forward_profile([body], k)
+    t = dev.upload(v)
+    other = sc.random_record(rng, k + 20)
+    for head, cut in [(b"N" * 50, 30), (b"N" * 50, 50 + k - 1), (body[:k - 1] + b"N", k), (b"N" * (2 * k), k)]:
+        whole = head + body
+        ref = sc.score_record(whole, v, k, False, total)
+        assert all(w is None for w in sc.window_ids(whole[:cut], k)) and ref.windows > PIECE and math.isfinite(float(ref.log10_p))
+        first = dev.score([other, whole[:cut]], t, k, False, total)
+        assert int(first[1][1]) == 0 and math.isnan(first[0][1])
+        piece = whole[cut - (k - 1):]
+        got = probability.score_reads(*sc.pack([piece, other]), t, k, False, total, continues=True, none_scored=True)
+        assert (int(got[1][0]), int(got[2][0]), int(got[3][0])) == (ref.windows, ref.zero_windows, ref.min_count)
+        assert sc.error(got[0][0], ref) <= sc.bound(ref, PIECE, LANES, joins=1), (cut, len(head))
+        plain = dev.score([piece, other], t, k, False, total, continues=True)                # every window a transition: another number
+        assert int(plain[1][0]) == ref.windows
+        assert k == 1 or sc.error(plain[0][0], ref) > 100 * sc.bound(ref, PIECE, LANES, joins=1)          # (at k = 1 D(w) is total')
+        assert got[0][1] == plain[0][1] == dev.score([other], t, k, False, total)[0][0]       # (only record 0 is concerned)
+    # a piece shorter than k stays exempt from the length check under both flags; the new flag alone is refused
+    got = probability.score_reads(*sc.pack([body[:k - 1], body[:k + 3]]), t, k, False, total, continues=True, none_scored=True)
+    assert int(got[1][0]) == 0 and math.isnan(got[0][0])
+    bases, offsets = sc.pack([body[:k + 5]])
+    ok = dict(ptr=t.data_ptr(), k=k, canonical=0, total=total, a=0, bases=bases, offsets=offsets)
+    assert dev.raw(flags=_abi.KDB_SCORE_NONE_SCORED, **ok) == dev.ARG and dev.raw(flags=_abi.KDB_SCORE_CONTINUES | _abi.KDB_SCORE_NONE_SCORED, **ok) == dev.OK
+    with pytest.raises(ValueError):
+        probability.score_reads(bases, offsets, t, k, False, total, none_scored=True)
+
+
+def test_score_file_joins_a_record_that_begins_with_more_n_than_a_reader_block_holds(dev, tmp_path):
+    from kmerdb_amd import fileutil, probability
+    import ids_cases
+    k = 6
+    rng = np.random.default_rng(18)
+    records = [("n_first", b"N" * 150000 + sc.random_record(rng, 50000, p_n=0.0005)), ("short", sc.random_record(rng, 300)),
+               ("n_then_short", b"N" * 70000 + sc.random_record(rng, 40))]
+    fa = str(tmp_path / "n_first.fa")
+    ids_cases.write_fasta(fa, [(n, s.decode()) for n, s in records])
+    v, total = sc.forward_profile([s for _, s in records], k)
+    md = {"version": fileutil.VERSION, "metadata_blocks": 1, "k": k, "total_kmers": total, "unique_kmers": int(np.count_nonzero(v)), "unique_nullomers": 0,
+          "sorted": False, "tags": [], "files": []}
+    kdb = str(tmp_path / ("n_first.%d.kdb" % k))
+    fileutil.write_kdb(kdb, md, v)
+    rows = list(probability.score_file(fa, kdb, block_bytes=1 << 16))        # the Ns of the first record fill two blocks and more
+    one_block = list(probability.score_file(fa, kdb))
+    assert [r[0] for r in rows] == [n for n, _ in records] and [r[1] for r in rows] == [len(s) for _, s in records]
+    for row, whole, (_, s) in zip(rows, one_block, records):
+        ref = sc.score_record(s, v, k, False, total)
+        assert row[2:5] == whole[2:5] == (ref.windows, ref.zero_windows, ref.min_count) and ref.windows > 0
+        assert sc.error(row[5], ref) <= sc.bound(ref, PIECE, LANES, joins=len(s) // (1 << 16) + 1)
+        assert sc.error(whole[5], ref) <= sc.bound(ref, PIECE, LANES)
+
+
 def test_score_file_joins_a_fasta_record_longer_than_a_reader_block(dev, tmp_path):
     from kmerdb_amd import fileutil, probability
     import ids_cases
