@@ -328,6 +328,11 @@ class _Buffers:
         self.i = (self.i + 1) % self.depth
         return b
 
+    def unget(self):
+        """The buffer next() handed out last went unused (its chunk gave no block): it is the next one again, so that a block still
+        outlives the `depth` blocks after it and not merely the chunks."""
+        self.i = (self.i - 1) % self.depth
+
     def offsets(self, slot_of, n):
         """uint64 scratch of at least n entries tied to ring slot (reused: a fresh np.empty page-faults every block)."""
         key = id(slot_of)
@@ -398,8 +403,8 @@ class BlockReader:
     FASTA files are read whole by default (one block).  With `overlap` = k - 1 they are STREAMED in blocks: a record
     that does not end inside a block is held back and parsed with the next one; a record longer than a block comes in
     pieces -- the blocks after the first have .cont set and begin with the last `overlap` residues of the piece before
-    (Engine.submit(..., continues=True)).  After the iteration .total_reads / .min_len / .max_len / .sum_len hold the
-    record statistics of the file (pieces joined)."""
+    (Engine.submit(..., continues=True)) and bring at least one residue beyond them.  After the iteration
+    .total_reads / .min_len / .max_len / .sum_len hold the record statistics of the file (pieces joined)."""
 
     def __init__(self, path, want_ids=False, block_bytes=None, pinned=False, overlap=None, hold_ring=False):
         if type(path) is not str:
@@ -585,8 +590,15 @@ class BlockReader:
                 open_last = bool(in_out.value) and not eof and cut == len(text) and nr > 0
                 first = 0
                 region = out[pre:]                                  # where the parser wrote
+                if cont and int(offs[1]) == 0 and nr == 1 and open_last:
+                    # line ends alone while the record is open (blank lines, or the file's last line end in a chunk of its own: the end
+                    # of the file shows one read later): no piece -- one that repeats the overlap and brings no residue is no piece of
+                    # the record.  The record stays open, the overlap the same; only the parser's place in the line moves on.
+                    fa_state = in_out.value
+                    ring.unget()
+                    continue
                 if cont:
-                    if int(offs[1]) == 0 and not (nr == 1 and open_last):
+                    if int(offs[1]) == 0:
                         # nothing new for the open record (it ended at the chunk boundary): it is complete as it stands
                         self._account([pre], cont_prefix=pre)
                         first = 1
@@ -602,6 +614,7 @@ class BlockReader:
                 if nr <= 0:
                     if not open_last:
                         in_record, fa_state = False, 0
+                    ring.unget()
                     continue
                 ids = None
                 if want_ids:

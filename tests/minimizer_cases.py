@@ -125,6 +125,13 @@ def batch_minimizers(records, k, w, canonical=True, order=LEX):
     return np.array([o[0].size for o in out], dtype=np.uint64), cat(1, np.uint64), cat(0, np.uint32), cat(2, np.uint8)
 
 
+def minimizers_stub(bases, offsets, k, w, canonical=True, order="lexicographic", device=0):
+    """the restatement behind the signature of kmerdb_amd.minimizer.minimizers: the CPU tests put it in the device call's place"""
+    raw = bytes(bases)
+    o = [int(x) for x in offsets]
+    return batch_minimizers([raw[o[i]:o[i + 1]] for i in range(len(o) - 1)], k, w, canonical, {"lexicographic": LEX, "hashed": HASHED}[order])
+
+
 def batch_minimizers_flat(bases, offsets, k, w, canonical=True, order=LEX):
     """batch_minimizers for many short records at once, where every record has no start position or at least w of them (so that
     every run is w positions long): the keys of all residues in one array, the runs of w of the whole array, and of those the ones

@@ -118,6 +118,23 @@ def score_record(seq, v, k, canonical, total, a=0, continues=False):
     return out
 
 
+def score_reads_stub(bases, offsets, vector, k, canonical, total, pseudocount=0, continues=False, device=0, none_scored=False):
+    """the restatement behind the signature of kmerdb_amd.probability.score_reads, `vector` the counts on the host: the CPU tests put it
+    in the device call's place.  A continuing record 0 before which nothing was scored (none_scored) takes the initial term: that is
+    score_record's plain form.  log10_p is the exact sum rounded once."""
+    raw = bytes(bases)
+    o = [int(x) for x in offsets]
+    out = []
+    for r in range(len(o) - 1):
+        rec = raw[o[r]:o[r + 1]]
+        goes_on = bool(continues) and r == 0
+        if (len(rec) < k and not goes_on) or set(rec) - set(b"ACGTN"):
+            raise ValueError("a record shorter than k, or a residue outside ACGTN")
+        s = score_record(rec, vector, k, canonical, total, pseudocount, continues=goes_on and not none_scored)
+        out.append((float("nan") if s.log10_p is None else float(s.log10_p), s.windows, s.zero_windows, s.min_count))
+    return (np.array([x[0] for x in out], dtype=np.float64),) + tuple(np.array([x[i] for x in out], dtype=np.uint64) for i in (1, 2, 3))
+
+
 def float64_log10_p(score):
     """the same formula in plain float64 numpy, terms in window order; nan / -inf as the device gives them"""
     if not score.terms:

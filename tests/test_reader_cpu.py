@@ -43,11 +43,13 @@ def _join(blocks, ov):
 def test_fasta_streaming_reassembles_every_record(tmp_path, wrap):
     from kmerdb_amd import reader
     rng = np.random.Generator(np.random.PCG64(2))
-    for lens in ([10, 5000, 3, 0, 70000, 12, 1], [200000], [1, 1, 1], [9000] * 5):
+    for lens in ([10, 5000, 3, 0, 70000, 12, 1], [200000], [1, 1, 1], [9000] * 5, [0, 130, 0, 61, 200]):
         p = str(tmp_path / "s.fa")
         recs = _mkfa(p, lens, wrap, rng)
-        for B in (1000, 4096, 65536, 1 << 20):
-            for ov in (0, 11, 16):
+        size = os.path.getsize(p)
+        # (size - 1: the last chunk is the last line end alone; in a small file also every line end, and every line, a chunk of its own)
+        for B in [1000, 4096, 65536, 1 << 20, size - 1] + ([1, 7, 61, 62] if size < 20000 else [997]):
+            for ov in (0, 1, 11, 16):
                 rd = reader.BlockReader(p, want_ids=True, block_bytes=B, overlap=ov)
                 got, prefix = _join(rd, ov)
                 assert got == recs, (wrap, lens, B, ov)
@@ -57,6 +59,72 @@ def test_fasta_streaming_reassembles_every_record(tmp_path, wrap):
     rd = reader.BlockReader(p, want_ids=True)
     got, _ = _join(rd, 0)
     assert got == recs and rd.total_reads == len(recs)
+
+
+def _read(path, B, ov):
+    from kmerdb_amd import reader
+    rd = reader.BlockReader(path, want_ids=True, block_bytes=B, overlap=ov)
+    blocks = []
+    for blk in rd:
+        blocks.append(reader.Block(blk[0].copy(), blk[1].copy(), blk[2], blk.cont))
+    return rd, blocks
+
+
+@pytest.mark.parametrize("shape", ["n_blocks_and_one_byte", "n_blocks_and_two_bytes_crlf", "blank_lines_behind", "blank_lines_in_mid_record"])
+def test_no_continuation_piece_without_a_new_residue(tmp_path, shape):
+    """Line ends alone, in a chunk of their own while a record is open, are no piece of that record: the file's last line end (the end
+    of the file shows one read later), blank lines behind the last record, a run of blank lines inside one.  The statistics hold."""
+    B, n = 64, 3
+    rng = np.random.Generator(np.random.PCG64(5))
+    seq = lambda L: "".join(rng.choice(list("ACGT"), size=L))
+    if shape == "n_blocks_and_one_byte":
+        recs = [seq(n * B - 3)]
+        text = ">r\n" + recs[0] + "\n"
+        nblocks = n
+    elif shape == "n_blocks_and_two_bytes_crlf":
+        recs = [seq(n * B - 4)]
+        text = ">r\r\n" + recs[0] + "\r\n"
+        nblocks = n
+    elif shape == "blank_lines_behind":
+        recs = [seq(10), seq(n * B - 8 - 13 - 3)]
+        text = ">a\n" + recs[0] + "\n>b\n" + recs[1] + "\n" * (2 * B + 5)
+        nblocks = None
+    else:
+        recs = [seq(B + 20) + seq(30), seq(7)]
+        text = ">r\n" + recs[0][:B + 20] + "\n" + "\n" * (3 * B) + recs[0][B + 20:] + "\n>s\n" + recs[1] + "\n"
+        nblocks = None
+    p = str(tmp_path / "e.fa")
+    open(p, "wb").write(text.encode())
+    if shape.startswith("n_blocks"):
+        assert os.path.getsize(p) == n * B + (1 if "one" in shape else 2)
+    L = [len(r) for r in recs]
+    for ov in (0, 5, 20):
+        rd, blocks = _read(p, B, ov)
+        got, _ = _join(blocks, ov)                          # (asserts that every continuation piece brings something new)
+        assert got == recs, (shape, ov)
+        assert (rd.total_reads, rd.min_len, rd.max_len, rd.sum_len) == (len(L), min(L), max(L), sum(L)), (shape, ov)
+        assert nblocks is None or len(blocks) == nblocks
+        assert all(blk[2][0] is None for blk in blocks if blk.cont)
+        assert [i for blk in blocks for i in blk[2] if i is not None] == (["a", "b"] if shape == "blank_lines_behind" else ["r", "s"][:len(L)])
+
+
+def test_a_block_outlives_two_further_blocks_whatever_the_chunks_between(tmp_path):
+    """A chunk that gives no block (blank lines, text before the first header) takes no buffer of the ring: block i is intact when
+    block i + 2 has been produced (three buffers; Engine.submit_pinned reads block i until then)."""
+    from kmerdb_amd import reader
+    B = 64
+    rng = np.random.Generator(np.random.PCG64(6))
+    line = lambda L: "".join(rng.choice(list("ACGT"), size=L)) + "\n"
+    text = "junk\n" * 40 + ">r\n" + line(50) + "\n" * (3 * B) + line(40) + line(60) + "\n" * (2 * B) + line(90) + line(200) + ">s\n" + line(30)
+    p = str(tmp_path / "ring.fa")
+    open(p, "w").write(text)
+    for ov in (0, 9):
+        kept = []
+        for blk in reader.BlockReader(p, want_ids=True, block_bytes=B, overlap=ov):
+            kept.append((blk[0], blk[0].copy()))
+            for view, copy in kept[-3:]:
+                assert np.array_equal(view, copy), (ov, len(kept))
+        assert len(kept) >= 8
 
 
 def test_fastq_reader_statistics(golden_dir):
